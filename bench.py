@@ -1,6 +1,14 @@
 """jpge benchmark — BASELINE.json metric: MPixels/s encode (4K 4:2:0 Q=90).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k-frames|batch1080|16k-striped|ppm-files]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs
+if --dump-outputs is given (lengths, byte sums and a fixed sample of the .jpg bytes
+as .npy: dump_outputs) and prints the line: metric, value, unit, ms_per_step, the
+configuration and the host CPU use.  --full adds the legs that take runs of their
+own after the timed region (verification, D2H pass, solo kernel timing and the
+rooflines, latency, CPU baseline: the keys described below).
 
 Launch: `--gpus N` under torch.distributed.run uses its RANK/WORLD_SIZE; without a
 launcher (WORLD_SIZE unset) and N > 1 this script starts the N rank processes
@@ -23,7 +31,7 @@ Huffman-table build, entropy code + pack kernels, finished .jpg bytes in HBM):
   16k-striped (config 5): one 16384^2 frame per step, row-striped over the ranks.
   ppm-files  (SURVEY 8(f) rank 1): PPM files -> .jpg files (PCIe-inclusive).
 
-The 4k-frames line carries: `roofline` = the dominant kernel alone on the GPU (its
+With --full the 4k-frames line carries: `roofline` = the dominant kernel alone on the GPU (its
 exclusive time: a 1-lane encoder after the timed region, HIP events bound to the
 kernel's own dispatch; checked against the step: launches x duration <= ms_per_step),
 `roofline_dct_stage` = K1 alone (the BASELINE figure, with its HBM-read-only
@@ -82,6 +90,16 @@ def parse(argv=None):
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--width", type=int, default=W4K)
     ap.add_argument("--height", type=int, default=H4K)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: output verification, "
+                         "the D2H pass, solo kernel timing and the rooflines, single-frame latency, the CPU "
+                         "baseline (each can be narrowed with its own option below).  Without --full a run sets "
+                         "up, warms up, times the steps and prints the line; those options then have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step produced on rank 0 as DIR/<name>.npy "
+                         "(float64 / float32): lens (every output's length), byte_sums (every output's byte sum), "
+                         "sample (chunks of the .jpg bytes of a fixed, seeded choice of outputs), sample_slots and "
+                         "sample_offsets (where the chunks come from)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip the post-timing output verification")
     ap.add_argument("--d2h-steps", type=int, default=5, help="steps of the D2H-inclusive pass (0 = skip)")
@@ -119,7 +137,48 @@ def parse(argv=None):
                          "timing events (the in-situ diagnostic; events cost throughput and host CPU: a HIP "
                          "runtime thread waits on their signals, 0.69 CPU at every 64th frame, 0.04 at every "
                          "1024th)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: nothing but the headline figure
+        args.no_verify = args.no_cpu_baseline = True
+        args.d2h_steps = args.solo_batches = args.latency_calls = 0
+    return args
+
+
+# ---------------------------------------------------------------- output dump
+
+DUMP_SLOTS = 32          # outputs sampled: the first 32 and 32 more drawn with a fixed seed
+DUMP_CHUNK = 32 << 10    # bytes per sampled chunk; 4 chunks per sampled output (32 MiB as float32 in all)
+
+
+def dump_outputs(dirname: str, segs) -> None:
+    """--dump-outputs: the .jpg bytes the last timed step left its caller, one 1-D uint8
+    tensor per output in `segs` (device or host, cut to its length).  Every output's
+    length and byte sum, and of a fixed choice of outputs four chunks of the bytes: the
+    head, the tail (a changed bit anywhere before it shifts it) and two seeded places
+    between.  The choice depends on the number of outputs alone."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    n = len(segs)
+    lens = np.array([int(s.numel()) for s in segs], np.float64)
+    sums = torch.stack([s.sum(dtype=torch.int64) for s in segs]).cpu().numpy().astype(np.float64)
+    rng = np.random.default_rng(0x6A7067)
+    slots = sorted(set(range(min(n, DUMP_SLOTS))) | set(rng.choice(n, min(n, DUMP_SLOTS), replace=False).tolist()))
+    fracs = np.concatenate([[0.0, 1.0], rng.random(2)])
+    offs = np.zeros((len(slots), len(fracs)), np.float64)
+    buf = torch.zeros((len(slots), len(fracs), DUMP_CHUNK), dtype=torch.uint8, device=segs[0].device)
+    for a, i in enumerate(slots):
+        room = max(0, int(lens[i]) - DUMP_CHUNK)
+        for b, f in enumerate(fracs):
+            off = int(f * room)
+            m = min(DUMP_CHUNK, int(lens[i]) - off)
+            buf[a, b, :m] = segs[i][off:off + m]
+            offs[a, b] = off
+    for name, arr in (("lens", lens), ("byte_sums", sums), ("sample", buf.cpu().numpy().astype(np.float32)),
+                      ("sample_slots", np.array(slots, np.float64)), ("sample_offsets", offs)):
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 # ---------------------------------------------------------------- launch / ranks
@@ -720,6 +779,9 @@ def run_striped16k(args, rank, local, world, pg):
     rank_cpus = all_gather_floats(pg, (process_cpu_s() - pc0) / dt, world)
     dt = max_over_ranks(pg, dt)
     ms_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        PHASE("output dump")
+        dump_outputs(args.dump_outputs, [out[:int(n)]])
     # per-kernel rooflines: this rank's rows (the whole frame at N = 1) as one frame through
     # a 1-lane encoder with kernel events (the same kernels over the same pixels; a stripe's
     # own phases run them with the exchanges between)
@@ -782,6 +844,7 @@ def run_striped16k(args, rank, local, world, pg):
                                          if restart else
                                          "DC seeds, histogram sum/min, summaries; segments gathered to rank 0)")),
                        "restart_mcus": restart, "jpeg_bytes": int(n)},
+            "full": args.full,  # (False: the legs after the timed region were not run)
             "roofline": roofline,
             "roofline_dct_stage": dict(kernel="fdct_kernel", timing="solo", **stages_solo["fdct_kernel"])
             if stages_solo else None,
@@ -833,6 +896,8 @@ def run_ppm_files(args, rank, local, world, pg):
         barrier(pg)
         dt = max_over_ranks(pg, time.perf_counter() - t0)
         pixels = sum_over_ranks(pg, float(W * H * F * args.steps))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, [torch.from_numpy(np.fromfile(p, np.uint8)) for p in outs])
         if rank == 0:
             print(json.dumps({
                 "metric": f"MPixels/s encode from PPM files ({W}x{H} 4:2:0 Q={args.quality})",
@@ -958,6 +1023,9 @@ def run_batch1080(args, rank, local, world, pg):
     rank_cpus = all_gather_floats(pg, pcpu, world)
     if gather is not None and rank == 0:
         phase["lengths_wait"] = gather.lens_wait_s
+    if args.dump_outputs and rank == 0:  # (rank 0's own frames of the batch, in its output slots)
+        PHASE("output dump")
+        dump_outputs(args.dump_outputs, [segs[s_last][k][:lens[k]] for k in range(len(share))])
     # verification: every frame of the last step, as rank 0 holds it, equals the
     # host-path encode of that frame (rank 0's own frames are in its output slots)
     bad = 0
@@ -1020,6 +1088,7 @@ def run_batch1080(args, rank, local, world, pg):
             "rank0_phases_ms_per_step": {k: round(v / args.steps * 1e3, 3) for k, v in phase.items()},
             "lanes_per_rank": enc.lanes(),
             "devices": args.devices,
+            "full": args.full,  # (False: the legs after the timed region were not run)
             # the dominant kernel alone (rank 0's frames; exclusive time, checked against the step)
             "roofline": roofline,
             "roofline_dct_stage": dict(kernel="fdct_kernel", timing="solo", **stages_solo["fdct_kernel"])
@@ -1099,6 +1168,10 @@ def run_frames(args, rank, local, world, pg):
     dt_max = max_over_ranks(pg, dt)
     pixels = sum_over_ranks(pg, float(W * H * F * args.steps))
     value = pixels / dt_max / 1e6
+
+    if args.dump_outputs and rank == 0:
+        PHASE("output dump")
+        dump_outputs(args.dump_outputs, [outbuf[i * cap:i * cap + lens[i]] for i in range(F)])
 
     # Verification (after timing): every output slot of the last timed step equals
     # the host-path encode of its input frame (byte compare on the device).
@@ -1190,43 +1263,64 @@ def run_frames(args, rank, local, world, pg):
         lat.close()
         del hin, hout, dout
 
-    # per-kernel rooflines (HBM-bound integer/fp64 work; algorithmic bytes per launch)
-    npx = W * H
     avg_jpeg = total_bytes / (args.steps * F)
-    traffic = load_pmc_traffic(os.path.join(ROOT, "profiles"), W, H) if args.subsampling == 420 else {}
-    yh, yv = J.SUBSAMPLING[args.subsampling]
-    cb = 2.0 * 64 * (yh * yv + 2) / (64 * yh * yv)  # int16 coefficient bytes per pixel (4:2:0: 3)
-    # symbol records (record_bytes): written by K2, read by K3; per frame from every
-    # distinct input's histograms (whether or not a pass sampled it), averaged over the
-    # step's frames (frame i = input i mod D)
-    rbs = [record_bytes(enc.symbol_stats(host[d], quality=args.quality)[0]) for d in range(D)] if rank == 0 else [0.0]
-    rec_bytes = sum(rbs[i % len(rbs)] for i in range(F)) / F
-    alg, stage_alg = alg_bytes(npx, cb, rec_bytes, avg_jpeg)
+    rooflines = {}
+    if args.full:
+        # per-kernel rooflines (HBM-bound integer/fp64 work; algorithmic bytes per launch)
+        npx = W * H
+        traffic = load_pmc_traffic(os.path.join(ROOT, "profiles"), W, H) if args.subsampling == 420 else {}
+        yh, yv = J.SUBSAMPLING[args.subsampling]
+        cb = 2.0 * 64 * (yh * yv + 2) / (64 * yh * yv)  # int16 coefficient bytes per pixel (4:2:0: 3)
+        # symbol records (record_bytes): written by K2, read by K3; per frame from every
+        # distinct input's histograms (whether or not a pass sampled it), averaged over the
+        # step's frames (frame i = input i mod D)
+        rbs = ([record_bytes(enc.symbol_stats(host[d], quality=args.quality)[0]) for d in range(D)]
+               if rank == 0 else [0.0])
+        rec_bytes = sum(rbs[i % len(rbs)] for i in range(F)) / F
+        alg, stage_alg = alg_bytes(npx, cb, rec_bytes, avg_jpeg)
 
-    stages = kernel_rooflines(tm, alg, stage_alg, traffic, npx)  # in situ (lanes overlap: diagnostic)
-    stages_solo = kernel_rooflines(tm_solo, alg, stage_alg, traffic, npx) if tm_solo else None
-    stages_solo1 = kernel_rooflines(tm_solo1, alg, stage_alg, traffic, npx) if tm_solo1 else None
-    ms_step = dt_max / args.steps * 1e3
-    # The headline roofline: the dominant kernel (longest exclusive time) ALONE on the GPU
-    # (the solo pass), its duration from events bound to its own dispatch, so the figure
-    # can be recomputed from a rocprofv3 kernel trace.  In the timed region four lanes'
-    # kernels overlap, so an in-situ duration is wall time shared with the other lanes.
-    roofline = None
-    if stages_solo:
-        roofline = solo_headline(stages_solo, alg, F, ms_step)
-    elif stages["fdct_kernel"]["avg_kernel_ms"]:
-        # no solo pass (--solo-batches 0): the in-situ figure, labelled as such (lanes
-        # overlap, so it is shared wall time and carries no per-step check)
-        dominant = max(alg, key=lambda k: stages[k]["avg_kernel_ms"] or 0.0)
-        roofline = dict(kernel=dominant, timing="in situ (4 lanes overlap: shared wall time, not exclusive; "
-                                                "run with --solo-batches > 0 for the exclusive figure)",
-                        **stages[dominant])
-    # whole pipeline: every kernel's algorithmic bytes per frame, over the wall time
-    pipe_bytes = sum(b for b, _ in alg.values())
-    pipe_ach = pipe_bytes * F * args.steps * world / dt_max / 1e9
-    pipeline = {"bound": "hbm", "achieved": round(pipe_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(pipe_ach / HBM_PEAK_GBS, 4), "alg_bytes_per_frame": int(pipe_bytes),
-                "note": "sum of the kernels' algorithmic bytes per frame x frames / wall time (per GPU)"}
+        stages = kernel_rooflines(tm, alg, stage_alg, traffic, npx)  # in situ (lanes overlap: diagnostic)
+        stages_solo = kernel_rooflines(tm_solo, alg, stage_alg, traffic, npx) if tm_solo else None
+        stages_solo1 = kernel_rooflines(tm_solo1, alg, stage_alg, traffic, npx) if tm_solo1 else None
+        ms_step = dt_max / args.steps * 1e3
+        # The headline roofline: the dominant kernel (longest exclusive time) ALONE on the GPU
+        # (the solo pass), its duration from events bound to its own dispatch, so the figure
+        # can be recomputed from a rocprofv3 kernel trace.  In the timed region four lanes'
+        # kernels overlap, so an in-situ duration is wall time shared with the other lanes.
+        roofline = None
+        if stages_solo:
+            roofline = solo_headline(stages_solo, alg, F, ms_step)
+        elif stages["fdct_kernel"]["avg_kernel_ms"]:
+            # no solo pass (--solo-batches 0): the in-situ figure, labelled as such (lanes
+            # overlap, so it is shared wall time and carries no per-step check)
+            dominant = max(alg, key=lambda k: stages[k]["avg_kernel_ms"] or 0.0)
+            roofline = dict(kernel=dominant, timing="in situ (4 lanes overlap: shared wall time, not exclusive; "
+                                                    "run with --solo-batches > 0 for the exclusive figure)",
+                            **stages[dominant])
+        # whole pipeline: every kernel's algorithmic bytes per frame, over the wall time
+        pipe_bytes = sum(b for b, _ in alg.values())
+        pipe_ach = pipe_bytes * F * args.steps * world / dt_max / 1e9
+        pipeline = {"bound": "hbm", "achieved": round(pipe_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(pipe_ach / HBM_PEAK_GBS, 4), "alg_bytes_per_frame": int(pipe_bytes),
+                    "note": "sum of the kernels' algorithmic bytes per frame x frames / wall time (per GPU)"}
+        rooflines = {
+            # dominant kernel alone (exclusive time; see above)
+            "roofline": roofline,
+            # BASELINE.json's "% HBM roofline on DCT stage" (SURVEY 8(d): 6 B/px; read-only 3 B/px): the kernel alone
+            "roofline_dct_stage": dict(kernel="fdct_kernel", timing="solo", **stages_solo["fdct_kernel"])
+            if stages_solo else dict(kernel="fdct_kernel", timing="in situ", **stages["fdct_kernel"]),
+            "roofline_pipeline": pipeline,
+            "stages": stages,
+            "stages_solo": stages_solo,
+            "stages_solo_single_frame": stages_solo1,
+            "kernel_events": f"each kernel launch of a sampled frame (set) launched with its own HIP events bound "
+                             f"to its dispatch (hipExtLaunchKernel); figures per launch, a frame set's launch "
+                             f"covering frames_per_launch frames. stages: in situ, the set of every "
+                             f"{args.event_every}th frame in the timed region (4 lanes overlap: a diagnostic, not "
+                             f"exclusive time); stages_solo: every launch of {args.solo_batches} batches of {D} on a "
+                             f"1-lane encoder after the timed region, in the pipeline's frame sets of {set_size}; "
+                             f"stages_solo_single_frame: the same, one frame per launch",
+        }
 
     if rank == 0:
         line = {
@@ -1250,22 +1344,8 @@ def run_frames(args, rank, local, world, pg):
                 "parallelism": f"frames sharded over {world} GPU(s), no data-path collective",
                 "avg_jpeg_bytes": int(avg_jpeg),
             },
-            # dominant kernel alone (exclusive time; see above)
-            "roofline": roofline,
-            # BASELINE.json's "% HBM roofline on DCT stage" (SURVEY 8(d): 6 B/px; read-only 3 B/px): the kernel alone
-            "roofline_dct_stage": dict(kernel="fdct_kernel", timing="solo", **stages_solo["fdct_kernel"])
-            if stages_solo else dict(kernel="fdct_kernel", timing="in situ", **stages["fdct_kernel"]),
-            "roofline_pipeline": pipeline,
-            "stages": stages,
-            "stages_solo": stages_solo,
-            "stages_solo_single_frame": stages_solo1,
-            "kernel_events": f"each kernel launch of a sampled frame (set) launched with its own HIP events bound "
-                             f"to its dispatch (hipExtLaunchKernel); figures per launch, a frame set's launch "
-                             f"covering frames_per_launch frames. stages: in situ, the set of every "
-                             f"{args.event_every}th frame in the timed region (4 lanes overlap: a diagnostic, not "
-                             f"exclusive time); stages_solo: every launch of {args.solo_batches} batches of {D} on a "
-                             f"1-lane encoder after the timed region, in the pipeline's frame sets of {set_size}; "
-                             f"stages_solo_single_frame: the same, one frame per launch",
+            "full": args.full,  # (False: the rooflines and the legs after the timed region were not run)
+            **rooflines,
             "step_ms": {"min": round(min(step_t) * 1e3, 3), "median": round(sorted(step_t)[len(step_t) // 2] * 1e3, 3),
                         "max": round(max(step_t) * 1e3, 3)},
             "lanes": enc.lanes(),

@@ -11,7 +11,7 @@ for r in $(seq $rounds); do
     i=$((i + 1))
     o=gpurun_out/abe/v$i
     [ "$e" = "-" ] && e=""
-    env $e timeout -k 10 200 python3 bench.py ${AB_ARGS:---frames 1536 --steps 8} --warmup 2 --no-cpu-baseline --d2h-steps 0 --no-verify --solo-batches 2 > $o.json 2> $o.err || { echo "== [$e] failed"; tail -3 $o.err; exit 1; }
+    env $e timeout -k 10 200 python3 bench.py ${AB_ARGS:---frames 1536 --steps 8} --warmup 2 --no-cpu-baseline --d2h-steps 0 --no-verify --solo-batches 2 --full > $o.json 2> $o.err || { echo "== [$e] failed"; tail -3 $o.err; exit 1; }
     echo "[$e] $(python3 -c "
 import json;d=json.loads(open('$o.json').read().strip().splitlines()[-1])
 f=lambda s:{k[:6]: round(v['avg_kernel_ms']*1e3,2) for k,v in (d.get(s) or {}).items()}

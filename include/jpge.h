@@ -126,6 +126,36 @@ int jpge_set_restart_interval(jpge_ctx* ctx, uint32_t mcus);
  * returns the mode's planes; the stripe phases (jpge_stripe_*) need JPGE_S420_M. */
 int jpge_set_subsampling(jpge_ctx* ctx, int mode);
 
+/* Input layouts of 8-bit frames.  The .jpg of a frame in any of them is, byte for
+ * byte, the .jpg of the same pixels rearranged to interleaved RGB: only the
+ * transform kernel's loads differ, no repack pass runs. */
+#define JPGE_FMT_RGB8 0        /* interleaved R,G,B, 3 bytes per pixel (the default) */
+#define JPGE_FMT_BGR8 1        /* interleaved B,G,R */
+#define JPGE_FMT_RGBA8 2       /* interleaved R,G,B,A, 4 bytes per pixel; alpha ignored */
+#define JPGE_FMT_BGRA8 3       /* interleaved B,G,R,A; alpha ignored */
+#define JPGE_FMT_RGB8_PLANAR 4 /* planes R, G, B of `height` rows of `stride` bytes, 1 byte per
+                                  pixel, at rgb, rgb + plane_stride, rgb + 2*plane_stride */
+
+/* Input layout for the context's following jpge_encode_rgb8, jpge_encode_batch,
+ * jpge_fdct_quant and jpge_symbol_stats calls (their `rgb` then points at a frame in
+ * that layout), also on a group member's context (jpge_group_context), and so for
+ * jpge_group_encode_batch.  plane_stride: the planar layout's bytes between planes,
+ * 0 = stride * height of each frame (contiguous CHW); non-zero with an interleaved
+ * layout, or an unknown layout: JPGE_E_ARG.  A frame's stride of 0 means width * the
+ * layout's bytes per pixel (planar: width); a smaller stride is JPGE_E_ARG.  maxval
+ * scales the three colour channels as before.  The fast path needs the pointer, the
+ * stride and the plane stride 16-byte aligned; anything else works, slower.
+ * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
+ * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
+ * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
+ * the planar one; jpge_group_encode_striped needs JPGE_FMT_RGB8. */
+int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
+/* the current setting (plane_stride may be NULL) */
+int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride);
+/* bytes per pixel along a row and number of planes of a layout (host only; either
+ * pointer may be NULL); unknown layout: JPGE_E_ARG */
+int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes);
+
 /* Worst-case .jpg size for a frame, in any subsampling mode (header + 2x
  * worst-case entropy + RST markers + EOI). */
 size_t jpge_max_jpeg_bytes(uint32_t width, uint32_t height);

@@ -24,6 +24,9 @@ LIB_PATH = os.environ.get("JPGE_LIB") or os.path.join(_HERE, "lib", "libjpge.so"
 JPGE_DEVICE_INPUT = 1
 JPGE_DEVICE_OUTPUT = 2
 
+#: input layouts (jpge.h JPGE_FMT_*): interleaved (H, W, 3) / (H, W, 4) frames, or planar (3, H, W)
+JPGE_FMT_RGB8, JPGE_FMT_BGR8, JPGE_FMT_RGBA8, JPGE_FMT_BGRA8, JPGE_FMT_RGB8_PLANAR = 0, 1, 2, 3, 4
+
 #: subsampling modes (jpge.h JPGE_S*) -> (Y blocks across, Y blocks down) an MCU
 SUBSAMPLING = {420: (2, 2), 4200: (2, 2), 4201: (2, 2), 444: (1, 1), 422: (2, 1), 411: (4, 1)}
 
@@ -37,6 +40,7 @@ STATUS = {
 EXPORTS = (
     "jpge_strerror", "jpge_version", "jpge_device_count", "jpge_open", "jpge_open_ex", "jpge_close", "jpge_set_timing",
     "jpge_get_timing", "jpge_reset_timing", "jpge_get_lanes", "jpge_set_restart_interval", "jpge_set_subsampling",
+    "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info",
     "jpge_max_jpeg_bytes", "jpge_quality_tables", "jpge_encode_rgb8", "jpge_encode_batch",
     "jpge_fdct_quant", "jpge_symbol_stats", "jpge_huffman_table", "jpge_huffman_text", "jpge_parse_ppm",
     "jpge_ppm_info", "jpge_encode_file", "jpge_encode_files", "jpge_synth_rgb8", "jpge_arai_constants",
@@ -126,6 +130,9 @@ def lib() -> ctypes.CDLL:
         L.jpge_get_lanes.argtypes = [vp, ctypes.POINTER(i32)]
         L.jpge_set_restart_interval.argtypes = [vp, u32]
         L.jpge_set_subsampling.argtypes = [vp, i32]
+        L.jpge_set_input_format.argtypes = [vp, i32, sz]
+        L.jpge_get_input_format.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(sz)]
+        L.jpge_input_format_info.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         L.jpge_device_count.argtypes = [ctypes.POINTER(i32)]
         L.jpge_max_jpeg_bytes.restype = sz
         L.jpge_max_jpeg_bytes.argtypes = [u32, u32]
@@ -385,6 +392,24 @@ def arai_constants() -> tuple[np.ndarray, np.ndarray]:
     return a, s
 
 
+def input_format_info(fmt: int) -> tuple[int, int]:
+    """(bytes per pixel along a row, planes) of an input layout (JPGE_FMT_*); host only."""
+    b, n = ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().jpge_input_format_info(int(fmt), ctypes.byref(b), ctypes.byref(n)), "input_format_info")
+    return b.value, n.value
+
+
+def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
+    """(width, height, row stride in bytes) of a C-contiguous frame shaped for layout `fmt`:
+    (H, W, 3), (H, W, 4) or (3, H, W)."""
+    bpp, planes = input_format_info(fmt)
+    want = "(3, H, W)" if planes == 3 else f"(H, W, {bpp})"
+    if a.ndim != 3 or (a.shape[0] != 3 if planes == 3 else a.shape[2] != bpp):
+        raise ValueError(f"frame of shape {a.shape}: input layout {fmt} takes {want}")
+    h, w = (a.shape[1], a.shape[2]) if planes == 3 else (a.shape[0], a.shape[1])
+    return w, h, w * bpp
+
+
 def device_count() -> int:
     n = ctypes.c_int(0)
     lib().jpge_device_count(ctypes.byref(n))
@@ -422,6 +447,7 @@ class Encoder:
         self.device = device
         self._qcache = {}     # quality -> (qy, qc) byte tables
         self._desc = None     # (key, Frame array) of the last device batch
+        self._fmt = JPGE_FMT_RGB8
 
     def close(self) -> None:
         if self._ctx:
@@ -470,6 +496,19 @@ class Encoder:
         _check(lib().jpge_set_subsampling(self._ctx, int(mode)), "set_subsampling")
         self._sub = int(mode)
 
+    def set_input_format(self, fmt: int, plane_stride: int = 0) -> None:
+        """Input layout of the following encodes (JPGE_FMT_*): frames are then (H, W, 3),
+        (H, W, 4) or, planar, (3, H, W).  plane_stride: bytes between the planes of the
+        raw-pointer entries' planar frames (0 = stride * height)."""
+        _check(lib().jpge_set_input_format(self._ctx, int(fmt), int(plane_stride)), "set_input_format")
+        self._fmt = int(fmt)
+
+    def input_format(self) -> tuple[int, int]:
+        """(layout, plane stride) as set."""
+        f, ps = ctypes.c_int32(), ctypes.c_size_t()
+        _check(lib().jpge_get_input_format(self._ctx, ctypes.byref(f), ctypes.byref(ps)), "get_input_format")
+        return f.value, ps.value
+
     def lanes(self) -> int:
         n = ctypes.c_int32()
         _check(lib().jpge_get_lanes(self._ctx, ctypes.byref(n)), "get_lanes")
@@ -482,13 +521,14 @@ class Encoder:
         return np.ascontiguousarray(qy, np.uint8), np.ascontiguousarray(qc, np.uint8)
 
     def encode(self, rgb: np.ndarray, quality: int = 50, maxval: int = 255, qy=None, qc=None) -> bytes:
-        """Image::writeJPEG (Image.cpp:831-976) on an (H, W, 3) uint8 frame -> .jpg bytes."""
+        """Image::writeJPEG (Image.cpp:831-976) on an (H, W, 3) uint8 frame -> .jpg bytes
+        (the frame shaped for the input layout, set_input_format)."""
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        h, w = rgb.shape[:2]
+        w, h, stride = _frame_geom(rgb, self._fmt)
         qy, qc = self._tables(quality, qy, qc)
         out = np.empty(max_jpeg_bytes(w, h), np.uint8)
         n = ctypes.c_size_t()
-        _check(lib().jpge_encode_rgb8(self._ctx, _p(rgb), w, h, w * 3, int(maxval), _p(qy), _p(qc), _p(out),
+        _check(lib().jpge_encode_rgb8(self._ctx, _p(rgb), w, h, stride, int(maxval), _p(qy), _p(qc), _p(out),
                                       out.size, ctypes.byref(n), 0), "encode")
         return out[:n.value].tobytes()
 
@@ -504,6 +544,62 @@ class Encoder:
         _check(lib().jpge_encode_rgb8(self._ctx, rgb_ptr, w, h, stride, int(maxval), q[2], q[3], out_ptr, cap,
                                       ctypes.byref(n), int(flags)), "encode_rgb8")
         return n.value
+
+    def encode_tensor(self, t, quality: int = 50, out=None, order: str = "rgb", maxval: int = 255, layout=None):
+        """One torch uint8 tensor through jpge_encode_rgb8 without a repack: (3, H, W) is the
+        planar layout (plane stride t.stride(0)), (H, W, 3) and (H, W, 4) the interleaved ones
+        in channel order `order` ("rgb" or "bgr"; planar tensors are R, G, B).  Any row stride;
+        the inner dimension must have unit stride (else ValueError).  A device tensor is read
+        in place (JPGE_DEVICE_INPUT), a host tensor goes the host path.  Returns the .jpg
+        bytes, or, with `out` a uint8 tensor on the frame's device, writes them there and
+        returns their length.  The encoder's input layout is the same afterwards.
+        layout: "chw" or "hwc"; needed only for a (3, H, 3) or (3, H, 4) tensor, which
+        could be either (else ValueError)."""
+        if layout not in (None, "chw", "hwc"):
+            raise ValueError(f"layout {layout!r}: 'chw' or 'hwc'")
+        if order not in ("rgb", "bgr"):
+            raise ValueError(f"order {order!r}: 'rgb' or 'bgr'")
+        if t.dim() != 3 or t.element_size() != 1 or t.dtype.is_floating_point:
+            raise ValueError("encode_tensor takes a 3-dimensional uint8 tensor")
+        shape, st = tuple(t.shape), tuple(t.stride())
+        plane_stride = 0
+        hwc, chw = shape[2] in (3, 4), shape[0] == 3
+        if hwc and chw and layout is None:
+            raise ValueError(f"tensor of shape {shape} is (3, H, W) or (H, W, C): pass layout='chw' or 'hwc'")
+        if layout is not None:
+            hwc, chw = hwc and layout == "hwc", chw and layout == "chw"
+        if hwc:  # (H, W, C)
+            if st[2] != 1 or (st[1] != shape[2] and shape[1] > 1):  # (one pixel per row: any pixel stride)
+                raise ValueError(f"strides {st}: the inner dimension must have unit stride (pixels packed)")
+            h, w, stride = shape[0], shape[1], st[0]
+            fmt = {(3, "rgb"): JPGE_FMT_RGB8, (3, "bgr"): JPGE_FMT_BGR8, (4, "rgb"): JPGE_FMT_RGBA8,
+                   (4, "bgr"): JPGE_FMT_BGRA8}[(shape[2], order)]
+        elif chw:  # (3, H, W)
+            if order != "rgb":
+                raise ValueError("a planar (3, H, W) tensor is R, G, B")
+            if st[2] != 1:
+                raise ValueError(f"strides {st}: the inner dimension must have unit stride")
+            h, w, stride, plane_stride, fmt = shape[1], shape[2], st[1], st[0], JPGE_FMT_RGB8_PLANAR
+        else:
+            raise ValueError(f"tensor of shape {shape}: (3, H, W), (H, W, 3) or (H, W, 4)")
+        if stride < w * input_format_info(fmt)[0] and h > 1:
+            raise ValueError("rows overlap")
+        flags = JPGE_DEVICE_INPUT if t.is_cuda else 0
+        host_out = None
+        if out is None:
+            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            out_ptr, cap = _p(host_out), host_out.size
+        else:
+            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out: a contiguous uint8 device tensor")
+            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
+        prev = self.input_format()
+        self.set_input_format(fmt, plane_stride)
+        try:
+            n = self.encode_ptr(t.data_ptr(), w, h, stride, out_ptr, cap, quality, maxval, flags)
+        finally:
+            self.set_input_format(*prev)
+        return n if host_out is None else host_out[:n].tobytes()
 
     def encode_batch_dev(self, frames: list[tuple[int, int, int, int]], outs: list[tuple[int, int]],
                          quality: int = 50, maxval: int = 255,
@@ -531,11 +627,12 @@ class Encoder:
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         qy, qc = self._tables(quality, None, None)
         frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-        outs = [np.empty(max_jpeg_bytes(f.shape[1], f.shape[0]), np.uint8) for f in frames]
+        geom = [_frame_geom(f, self._fmt) for f in frames]
+        outs = [np.empty(max_jpeg_bytes(w, h), np.uint8) for w, h, _ in geom]
         arr = (Frame * len(frames))()
-        for i, (f, o) in enumerate(zip(frames, outs)):
-            arr[i].rgb, arr[i].width, arr[i].height = _p(f), f.shape[1], f.shape[0]
-            arr[i].stride, arr[i].maxval, arr[i].out, arr[i].cap = f.shape[1] * 3, maxval, _p(o), o.size
+        for i, (f, o, (w, h, stride)) in enumerate(zip(frames, outs, geom)):
+            arr[i].rgb, arr[i].width, arr[i].height = _p(f), w, h
+            arr[i].stride, arr[i].maxval, arr[i].out, arr[i].cap = stride, maxval, _p(o), o.size
         _check(lib().jpge_encode_batch(self._ctx, arr, len(frames), _p(qy), _p(qc), 0), "encode_batch")
         return [outs[i][:arr[i].len].tobytes() for i in range(len(frames))]
 
@@ -543,14 +640,14 @@ class Encoder:
         """Stage dump: quantised coefficients (before DC diff) -> (Y, Cb, Cr) arrays of shape
         (nblocks, 64), blocks in raster order, natural order within a block."""
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        h, w = rgb.shape[:2]
+        w, h, stride = _frame_geom(rgb, self._fmt)
         yh, yv = SUBSAMPLING[getattr(self, "_sub", 420)]
         mw, mh = -(-w // (8 * yh)), -(-h // (8 * yv))  # MCUs across / down
         y = np.zeros((mw * yh * mh * yv, 64), np.int16)
         cb = np.zeros((mw * mh, 64), np.int16)
         cr = np.zeros_like(cb)
         qy, qc = self._tables(quality, qy, qc)
-        _check(lib().jpge_fdct_quant(self._ctx, _p(rgb), w, h, w * 3, int(maxval), _p(qy), _p(qc), _p(y), _p(cb),
+        _check(lib().jpge_fdct_quant(self._ctx, _p(rgb), w, h, stride, int(maxval), _p(qy), _p(qc), _p(y), _p(cb),
                                      _p(cr), 0), "fdct_quant")
         return y, cb, cr
 
@@ -656,11 +753,11 @@ class Encoder:
 
     def symbol_stats(self, rgb: np.ndarray, quality: int = 50, maxval: int = 255):
         rgb = np.ascontiguousarray(rgb, np.uint8)
-        h, w = rgb.shape[:2]
+        w, h, stride = _frame_geom(rgb, self._fmt)
         qy, qc = self._tables(quality, None, None)
         counts = np.zeros(1024, np.uint32)
         first = np.zeros(1024, np.uint64)
-        _check(lib().jpge_symbol_stats(self._ctx, _p(rgb), w, h, w * 3, int(maxval), _p(qy), _p(qc), _p(counts),
+        _check(lib().jpge_symbol_stats(self._ctx, _p(rgb), w, h, stride, int(maxval), _p(qy), _p(qc), _p(counts),
                                        _p(first), 0), "symbol_stats")
         return counts.reshape(4, 256), first.reshape(4, 256)
 
@@ -673,6 +770,7 @@ class Group:
         devs = (ctypes.c_int * len(devices))(*devices)
         self._g = ctypes.c_void_p()
         _check(lib().jpge_group_open(len(devices), devs, int(lanes), ctypes.byref(self._g)), "group_open")
+        self._fmt = JPGE_FMT_RGB8
         _live_encoders.add(self)
 
     def close(self) -> None:
@@ -695,15 +793,25 @@ class Group:
     def set_restart(self, mcus: int) -> None:
         _check(lib().jpge_group_set_restart_interval(self._g, int(mcus)), "group_set_restart_interval")
 
+    def set_input_format(self, fmt: int, plane_stride: int = 0) -> None:
+        """Input layout of every member's context (jpge_set_input_format): for encode_batch;
+        encode_striped needs JPGE_FMT_RGB8."""
+        for m in range(self.size()[0]):
+            c = ctypes.c_void_p()
+            _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
+            _check(lib().jpge_set_input_format(c, int(fmt), int(plane_stride)), "set_input_format")
+        self._fmt = int(fmt)
+
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         """Config 4: frame i on member i mod N."""
         qy, qc = quality_tables(quality)
         frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-        outs = [np.empty(max_jpeg_bytes(f.shape[1], f.shape[0]), np.uint8) for f in frames]
+        geom = [_frame_geom(f, self._fmt) for f in frames]
+        outs = [np.empty(max_jpeg_bytes(w, h), np.uint8) for w, h, _ in geom]
         arr = (Frame * len(frames))()
-        for i, (f, o) in enumerate(zip(frames, outs)):
-            arr[i].rgb, arr[i].width, arr[i].height = _p(f), f.shape[1], f.shape[0]
-            arr[i].stride, arr[i].maxval, arr[i].out, arr[i].cap = f.shape[1] * 3, maxval, _p(o), o.size
+        for i, (f, o, (w, h, stride)) in enumerate(zip(frames, outs, geom)):
+            arr[i].rgb, arr[i].width, arr[i].height = _p(f), w, h
+            arr[i].stride, arr[i].maxval, arr[i].out, arr[i].cap = stride, maxval, _p(o), o.size
         _check(lib().jpge_group_encode_batch(self._g, arr, len(frames), _p(qy), _p(qc), 0), "group_encode_batch")
         return [outs[i][:arr[i].len].tobytes() for i in range(len(frames))]
 

@@ -180,7 +180,7 @@ const char* jpge_strerror(int s) {
     }
 }
 
-int jpge_version(void) { return 100; }
+int jpge_version(void) { return 101; }
 
 int jpge_device_count(int* n) {
     if (!n) return JPGE_E_ARG;
@@ -263,6 +263,29 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode) {
     return ctx->enc->set_subsampling(mode) ? JPGE_E_ARG : JPGE_OK;
 }
 
+int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride) {
+    CtxUse use(ctx);
+    if (!use) return JPGE_E_ARG;
+    std::lock_guard<std::recursive_mutex> l(ctx->enc->call_mutex());
+    return ctx->enc->set_input_format(format, plane_stride) ? JPGE_E_ARG : JPGE_OK;
+}
+
+int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride) {
+    CtxUse use(ctx);
+    if (!use || !format) return JPGE_E_ARG;
+    std::lock_guard<std::recursive_mutex> l(ctx->enc->call_mutex());
+    *format = ctx->enc->input_format();
+    if (plane_stride) *plane_stride = ctx->enc->input_plane_stride();
+    return JPGE_OK;
+}
+
+int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes) {
+    if (format < 0 || format >= jpge::kFmtCount) return JPGE_E_ARG;
+    if (bytes_per_pixel) *bytes_per_pixel = (int)jpge::fmt_bpp(format);
+    if (planes) *planes = (int)jpge::fmt_planes(format);
+    return JPGE_OK;
+}
+
 size_t jpge_max_jpeg_bytes(uint32_t w, uint32_t h) { return jpge::Encoder::max_jpeg_bytes(w, h); }
 
 int jpge_quality_tables(int quality, uint8_t qy[64], uint8_t qc[64]) {
@@ -271,17 +294,25 @@ int jpge_quality_tables(int quality, uint8_t qy[64], uint8_t qc[64]) {
     return JPGE_OK;
 }
 
-int jpge_encode_rgb8(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride, int maxval,
-                     const uint8_t qy[64], const uint8_t qc[64], uint8_t* out, size_t cap, size_t* len,
-                     uint32_t flags) {
+// jpge_encode_rgb8; use_format: in the context's input layout (the PPM entries: RGB8)
+static int encode_pixels(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride, int maxval,
+                         const uint8_t qy[64], const uint8_t qc[64], uint8_t* out, size_t cap, size_t* len,
+                         uint32_t flags, bool use_format) {
     CtxUse use(ctx);
     if (!use || !rgb || !qy || !qc || !out || !len) return JPGE_E_ARG;
     jpge::FrameDesc f = frame(rgb, w, h, stride, maxval);
+    if (use_format) ctx->enc->apply_input_format(f);
     f.out = out;
     f.cap = cap;
     int st = ctx->enc->encode(f, qy, qc, flags);
     *len = f.len;
     return st;
+}
+
+int jpge_encode_rgb8(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride, int maxval,
+                     const uint8_t qy[64], const uint8_t qc[64], uint8_t* out, size_t cap, size_t* len,
+                     uint32_t flags) {
+    return encode_pixels(ctx, rgb, w, h, stride, maxval, qy, qc, out, cap, len, flags, true);
 }
 
 int jpge_encode_batch(jpge_ctx* ctx, jpge_frame* frames, int n, const uint8_t qy[64], const uint8_t qc[64],
@@ -291,6 +322,7 @@ int jpge_encode_batch(jpge_ctx* ctx, jpge_frame* frames, int n, const uint8_t qy
     std::vector<jpge::FrameDesc> fd(n);
     for (int i = 0; i < n; ++i) {
         fd[i] = frame(frames[i].rgb, frames[i].width, frames[i].height, frames[i].stride, frames[i].maxval);
+        ctx->enc->apply_input_format(fd[i]);
         fd[i].out = frames[i].out;
         fd[i].cap = frames[i].cap;
     }
@@ -307,7 +339,9 @@ int jpge_fdct_quant(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, s
                     uint32_t flags) {
     CtxUse use(ctx);
     if (!use || !rgb || !qy || !qc || !cy || !ccb || !ccr) return JPGE_E_ARG;
-    return ctx->enc->fdct_quant(frame(rgb, w, h, stride, maxval), qy, qc, flags, cy, ccb, ccr);
+    jpge::FrameDesc f = frame(rgb, w, h, stride, maxval);
+    ctx->enc->apply_input_format(f);
+    return ctx->enc->fdct_quant(f, qy, qc, flags, cy, ccb, ccr);
 }
 
 int jpge_symbol_stats(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, size_t stride, int maxval,
@@ -315,7 +349,9 @@ int jpge_symbol_stats(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h,
                       uint32_t flags) {
     CtxUse use(ctx);
     if (!use || !rgb || !qy || !qc || !counts || !first) return JPGE_E_ARG;
-    return ctx->enc->symbol_stats(frame(rgb, w, h, stride, maxval), qy, qc, flags, counts, first);
+    jpge::FrameDesc f = frame(rgb, w, h, stride, maxval);
+    ctx->enc->apply_input_format(f);
+    return ctx->enc->symbol_stats(f, qy, qc, flags, counts, first);
 }
 
 int jpge_concat_segments(int device, void* stream, const uint8_t* const* segs, const size_t* lens, int n,
@@ -412,8 +448,8 @@ int jpge_encode_file(jpge_ctx* ctx, const char* ppm_path, const char* jpg_path, 
     jpge::quality_tables(quality, qy, qc);
     std::vector<uint8_t> out(jpge::Encoder::max_jpeg_bytes(img.width, img.height));
     size_t len = 0;
-    st = jpge_encode_rgb8(ctx, img.rgb.data(), img.width, img.height, 0, img.maxval, qy, qc, out.data(),
-                          out.size(), &len, 0);
+    st = encode_pixels(ctx, img.rgb.data(), img.width, img.height, 0, img.maxval, qy, qc, out.data(), out.size(),
+                       &len, 0, false);
     if (st) return st;
     std::ofstream f(jpg_path, std::ios::binary);
     if (!f.is_open()) return JPGE_E_IO;

@@ -318,6 +318,8 @@ struct Encoder::Slot {
     // per-frame state between phases
     const uint8_t* in_dev = nullptr;
     size_t in_stride = 0;
+    int in_fmt = kFmtRgb8;         // the input's layout (kernels.hpp kFmt*)
+    size_t in_plane_stride = 0;
     uint8_t* out_dev = nullptr;
     size_t out_cap = 0;
     size_t hdr_len = 0;
@@ -417,6 +419,14 @@ struct Encoder::Lane {
 int Encoder::set_restart(uint32_t mcus) {
     if (mcus > 65535) return kErrArg;  // DRI carries a 16-bit interval
     restart_mcus_ = mcus;
+    return kOk;
+}
+
+int Encoder::set_input_format(int fmt, size_t plane_stride) {
+    if (fmt < 0 || fmt >= kFmtCount) return kErrArg;
+    if (plane_stride && fmt != kFmtRgb8Planar) return kErrArg;
+    fmt_ = fmt;
+    plane_stride_ = plane_stride;
     return kOk;
 }
 
@@ -668,6 +678,8 @@ FdctArgs Encoder::fdct_args(Slot& s, int maxval, Slot* imp) {
     FdctArgs a;
     a.rgb = s.in_dev;
     a.stride = s.in_stride;
+    a.fmt = s.in_fmt;
+    a.plane_stride = s.in_plane_stride;
     a.g = s.g;
     a.maxval = maxval;
     a.solo = lanes_.size() == 1;  // (several lanes: K1 runs beside other frames' kernels)
@@ -760,11 +772,14 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     if (!f.rgb || f.width == 0 || f.height == 0 || f.width > 65535 || f.height > 65535) return kErrArg;
     if (f.maxval < 1 || f.maxval > 255) return kErrRange;
     const Geometry g = geometry(f.width, f.height, mode_);
-    const size_t row = (size_t)f.width * 3;
+    if (f.fmt < 0 || f.fmt >= kFmtCount || (f.plane_stride && f.fmt != kFmtRgb8Planar)) return kErrArg;
+    const size_t row = (size_t)f.width * fmt_bpp(f.fmt);
     const size_t stride = f.stride ? f.stride : row;
     if (stride < row) return kErrArg;
+    const size_t planes = fmt_planes(f.fmt);
+    const size_t plane_stride = f.plane_stride ? f.plane_stride : stride * f.height;  // (planar)
     const size_t dev_pitch = align_up(row, 16);
-    const size_t in_bytes = (flags & kFlagDeviceInput) ? 0 : dev_pitch * f.height;
+    const size_t in_bytes = (flags & kFlagDeviceInput) ? 0 : planes * dev_pitch * f.height;
     const size_t out_cap = (flags & kFlagDeviceOutput) ? 0 : max_jpeg_bytes(f.width, f.height);
     for (int i = 0; i < 64; ++i)
         if (!qy[i] || !qc[i]) return kErrArg;
@@ -773,16 +788,24 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     std::memcpy(s.qy, qy, 64);
     std::memcpy(s.qc, qc, 64);
     s.g = g;
+    s.in_fmt = f.fmt;
     if (flags & kFlagDeviceInput) {
         s.in_dev = f.rgb;
         s.in_stride = stride;
+        s.in_plane_stride = planes > 1 ? plane_stride : 0;
     } else {
-        if (stride == dev_pitch)  // one linear copy (a 2D copy can fall back to a slower engine path)
-            JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, dev_pitch * f.height, hipMemcpyHostToDevice, s.stream));
+        // (planar: the planes one after the other, dev_pitch * height bytes each)
+        const size_t dev_plane = dev_pitch * f.height;
+        if (stride == dev_pitch && (planes == 1 || plane_stride == dev_plane))
+            // one linear copy (a 2D copy can fall back to a slower engine path)
+            JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, planes * dev_plane, hipMemcpyHostToDevice, s.stream));
         else
-            JPGE_HIP(hipMemcpy2DAsync(s.d_in, dev_pitch, f.rgb, stride, row, f.height, hipMemcpyHostToDevice, s.stream));
+            for (size_t c = 0; c < planes; ++c)
+                JPGE_HIP(hipMemcpy2DAsync(s.d_in + c * dev_plane, dev_pitch, f.rgb + c * plane_stride, stride, row,
+                                          f.height, hipMemcpyHostToDevice, s.stream));
         s.in_dev = s.d_in;
         s.in_stride = dev_pitch;
+        s.in_plane_stride = planes > 1 ? dev_plane : 0;
     }
     if (flags & kFlagDeviceOutput) {
         s.out_dev = f.out;
@@ -1210,7 +1233,8 @@ int Encoder::batch_set_size(const FrameDesc* fr, int n) const {
     const FrameDesc& f0 = fr[0];
     if (!f0.width || !f0.height || f0.width > 65535 || f0.height > 65535) return 1;
     for (int i = 1; i < n; ++i)
-        if (fr[i].width != f0.width || fr[i].height != f0.height || (fr[i].maxval == 255) != (f0.maxval == 255))
+        if (fr[i].width != f0.width || fr[i].height != f0.height || (fr[i].maxval == 255) != (f0.maxval == 255) ||
+            fr[i].fmt != f0.fmt)
             return 1;
     const bool placed_in_code = (ext_place_ > 0 || (ext_place_ < 0 && lanes_.size() > 1)) && place_in_code_;
     if (!placed_in_code || restart_mcus_ || layout(geometry(f0.width, f0.height, mode_)).grid() > kPlaceInCodeMaxWgs)
@@ -1527,10 +1551,11 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     JPGE_HIP(hipSetDevice(device_));
     if (!d.rgb || !last_dc || d.width == 0 || d.height == 0 || d.width > 65535 || d.height > 65535) return kErrArg;
     if (mode_ != 420) return kErrArg;  // stripes are S420_m (the reference's subsampling)
+    if (fmt_ == kFmtRgb8Planar) return kErrArg;  // and interleaved (the stripe pointer is one row of pixels)
     if (d.maxval < 1 || d.maxval > 255) return kErrRange;
     const uint32_t mh_img = (d.height + 15) / 16;
     if (d.mcu_rows == 0 || d.mcu_row0 >= mh_img || d.mcu_rows > mh_img - d.mcu_row0) return kErrArg;
-    const size_t row = (size_t)d.width * 3, stride = d.stride ? d.stride : row;
+    const size_t row = (size_t)d.width * fmt_bpp(fmt_), stride = d.stride ? d.stride : row;
     if (stride < row) return kErrArg;
     for (int i = 0; i < 64; ++i)
         if (!qy[i] || !qc[i]) return kErrArg;
@@ -1545,6 +1570,8 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     s.g = g;
     s.in_dev = d.rgb;
     s.in_stride = stride;
+    s.in_fmt = fmt_;
+    s.in_plane_stride = 0;
     s.img_w = d.width;
     s.img_h = d.height;
     s.seed = DcSeed();

@@ -29,8 +29,13 @@ constexpr uint32_t kFlagCoefficients = 1u << 30;  // (internal) the frame's coef
 struct FrameDesc {
     const uint8_t* rgb = nullptr;
     uint32_t width = 0, height = 0;
-    size_t stride = 0;  // bytes per input row (0 = width*3)
+    size_t stride = 0;  // bytes per input row (0 = width * the layout's bytes per pixel)
     int maxval = 255;
+    // input layout (kernels.hpp kFmt*); planar: plane c at rgb + c * plane_stride
+    // (0 = stride * height).  The C ABI's pixel entries fill these from the context's
+    // setting; the PPM entries leave the default.
+    int fmt = kFmtRgb8;
+    size_t plane_stride = 0;
     uint8_t* out = nullptr;
     size_t cap = 0;
     size_t len = 0;
@@ -120,6 +125,18 @@ class Encoder {
     // reference's writeJPEG), 444, 422, 411, 4200 (S420), 4201 (S420_lm); stripes are 420 only
     int set_subsampling(int mode);
     int subsampling() const { return mode_; }
+    // input layout of the following pixel encodes (jpge.h JPGE_FMT_*; plane_stride: planar
+    // only, 0 = stride * height of each frame); the stripe phases take the interleaved ones
+    int set_input_format(int fmt, size_t plane_stride);
+    int input_format() const { return fmt_; }
+    size_t input_plane_stride() const { return plane_stride_; }
+    // the setting, written into a frame's description (the pair read under the call mutex,
+    // which set_input_format's callers hold)
+    void apply_input_format(FrameDesc& f) {
+        std::lock_guard<std::recursive_mutex> l(call_mu_);
+        f.fmt = fmt_;
+        f.plane_stride = plane_stride_;
+    }
 
     int lanes() const { return (int)lanes_.size(); }
 
@@ -181,6 +198,8 @@ class Encoder {
     uint32_t stats_wgs_ = 0;    // JPGE_STATS_WGS: statistics workgroup count (diagnostics; clamped)
     uint32_t restart_mcus_ = 0; // restart interval (jpge_set_restart_interval)
     int mode_ = 420;            // subsampling mode (jpge_set_subsampling)
+    int fmt_ = kFmtRgb8;        // input layout (jpge_set_input_format)
+    size_t plane_stride_ = 0;
     // entropy workgroups: the override, else 512 for a single lane's lone frames (their
     // latency: -5 us at 4K) and seg_layout's default (384, or 2 tiles per workgroup under
     // 768 tiles) beside other lanes (+3% throughput) and for a single lane's frame sets

@@ -1,4 +1,4 @@
-// K1 fdct_kernel (gfx950): RGB8 -> YCbCr -> 4:2:0 (S420_m) -> Arai FDCT (fp64)
+// K1 fdct_kernel (gfx950): RGB8 (or another input layout, see "input layouts" below) -> YCbCr -> 4:2:0 (S420_m) -> Arai FDCT (fp64)
 // -> quantise -> int16 coefficients (natural order, MCU-interleaved blocks).
 //
 // One wavefront owns a tile of 4 MCUs (64x16 px) staged in LDS for the column
@@ -162,6 +162,97 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
     b = __builtin_bit_cast(double, ((uint64_t)hi[1] << 32) | lo[1]);
 }
 
+// ---- input layouts ----
+// This file is built once per load shape (kernels.hpp kShape*; JPGE_K1_SHAPE, default
+// the RGB8 shape): the shape decides what a lane loads for its 16-pixel run and how the
+// run becomes 16 staged words R | G<<8 | B<<16.  Everything after the staging is the
+// same code in every build.  The kernels have internal linkage, so each build has its
+// own; the RGB8 build also holds the launch entry points, which dispatch by shape.
+#ifndef JPGE_K1_SHAPE
+#define JPGE_K1_SHAPE 0
+#endif
+constexpr int kShape = JPGE_K1_SHAPE;
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapePlanar, "JPGE_K1_SHAPE");
+constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kShape == kShapePlanar ? 1u : 3u;  // bytes per pixel along a row
+constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
+constexpr uint32_t kSelRgbx = 0x0C020100u, kSelBgrx = 0x0C000102u;  // perm selectors of a 4-byte pixel (0x0c: zero)
+
+// perm selector of a 3-byte pixel starting at byte o8 of a word pair
+__device__ __forceinline__ constexpr uint32_t sel3(uint32_t o8) {
+    return kShape == kShapeBgr8 ? 0x0C000000u | (o8 << 16) | ((o8 + 1) << 8) | (o8 + 2)
+                                : 0x0C000000u | ((o8 + 2) << 16) | ((o8 + 1) << 8) | o8;
+}
+// The prefetched run of a lane as 16 staged words, 4-byte and planar shapes: v0..v3 are
+// the four loads, or v0, v1, v2 the R, G, B planes' 16 bytes.  (The 3-byte shapes unpack
+// in the kernels.)
+__device__ __forceinline__ void unpack_run(const uint4& v0, const uint4& v1, const uint4& v2, const uint4& v3,
+                                           uint32_t sel4, uint32_t px[16]) {
+    if constexpr (kShape == kShapeX4) {
+        // the loaded word, alpha cleared (RGBA) or bytes 2,1,0 (BGRA): one perm either way
+        const uint32_t wd[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w,
+                                 v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) px[i] = __builtin_amdgcn_perm(0u, wd[i], sel4);
+    } else if constexpr (kShape == kShapePlanar) {
+        const uint32_t r[4] = {v0.x, v0.y, v0.z, v0.w}, g[4] = {v1.x, v1.y, v1.z, v1.w}, b[4] = {v2.x, v2.y, v2.z, v2.w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t o8 = (uint32_t)(i & 3);
+            const uint32_t rg = __builtin_amdgcn_perm(g[i >> 2], r[i >> 2], 0x0C0C0000u | ((4 + o8) << 8) | o8);
+            px[i] = __builtin_amdgcn_perm(b[i >> 2], rg, 0x0C000100u | ((4 + o8) << 16));
+        }
+    }
+}
+
+// One pixel of the clamped edge path: row sy, column sx (inside the frame).
+__device__ __forceinline__ uint32_t edge_pixel(const uint8_t* rgb, uint64_t stride, uint64_t plane_stride,
+                                               uint32_t sel4, uint32_t sy, uint32_t sx) {
+    const uint8_t* p = rgb + (uint64_t)sy * stride + (uint64_t)sx * kBpp;
+    if constexpr (kShape == kShapePlanar)
+        return (uint32_t)p[0] | ((uint32_t)p[plane_stride] << 8) | ((uint32_t)p[2 * plane_stride] << 16);
+    else if constexpr (kShape == kShapeBgr8)
+        return (uint32_t)p[2] | ((uint32_t)p[1] << 8) | ((uint32_t)p[0] << 16);
+    else if constexpr (kShape == kShapeX4)  // (byte loads: the pixel may be unaligned)
+        return __builtin_amdgcn_perm(0u, (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16), sel4);
+    else
+        return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+}
+
+// Descriptors of the pixel loads: the frame's rows (planar: one per plane; the others
+// repeat the first and are unused).  A lane's loads of a tile on the fast path end
+// inside their row, so the range is the last row's end.
+struct RgbRsrc {
+    __amdgpu_buffer_rsrc_t p0;
+#if JPGE_K1_SHAPE == 3
+    __amdgpu_buffer_rsrc_t p1, p2;
+#endif
+};
+__device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride, uint64_t plane_stride, uint32_t gw,
+                                            uint32_t gh) {
+    const int range = (int)(uint32_t)((uint64_t)stride * (gh - 1) + (uint64_t)kBpp * gw);
+    uint8_t* b = const_cast<uint8_t*>(rgb);
+    RgbRsrc r;
+    r.p0 = __builtin_amdgcn_make_buffer_rsrc(b, 0, range, 0x00020000);
+#if JPGE_K1_SHAPE == 3
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, range, 0x00020000);
+    r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + 2 * plane_stride, 0, range, 0x00020000);
+#endif
+    return r;
+}
+// the lane's run at buffer offset off (kOob: zeros)
+__device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint4& v0, uint4& v1, uint4& v2, uint4& v3) {
+#if JPGE_K1_SHAPE == 3
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, off, 0, 0));
+    v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, off, 0, 0));
+#else
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
+    v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 32, 0, 0));
+    if constexpr (kShape == kShapeX4) v3 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 48, 0, 0));
+#endif
+}
+
 template <bool kExact, int kWaves, int kFilt, int kN>
 __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN> fs) {
     const uint32_t set_f = set_member<kN>(fs.wg0, fs.n, blockIdx.x);  // (frame sets: kernels.hpp)
@@ -174,6 +265,16 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     uint64_t stride_ = a.stride;
     uint32_t gw_ = a.g.width, gh_ = a.g.height;
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
+    uint64_t ps_ = 0;                // planar: the plane pitch
+    uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
+    if constexpr (kShape == kShapePlanar) {
+        ps_ = a.plane_stride;
+        asm volatile("" : "+s"(ps_));
+    }
+    if constexpr (kShape == kShapeX4) {
+        sel4_ = a.fmt == kFmtBgra8 ? kSelBgrx : kSelRgbx;
+        asm volatile("" : "+s"(sel4_));
+    }
     constexpr int kK1Threads = kWaves * 64;
     __shared__ K1Lds<kWaves> lds;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;  // wv: 0..15
@@ -183,17 +284,15 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     const uint32_t tiles_per_row = (mw + 3) / 4;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    const bool aligned = (((uintptr_t)rgb_ | stride_) & 15) == 0;
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0;
     const int r16 = lane >> 2, c16 = lane & 3;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;     // DCT: lane -> (block of the round, column)
 
     // Pixels and coefficients move through buffer descriptors: an out-of-range
     // offset (kOob) makes a load return zeros and drops a store, so every tile
-    // issues the same 3 loads and 3 stores with no branch around them, and the
+    // issues the same 3 loads (4-byte pixels: 4) and 3 stores with no branch around them, and the
     // wait for the prefetched pixels leaves the previous tile's stores in flight.
-    const __amdgpu_buffer_rsrc_t rgb_rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(rgb_), 0, (int)(uint32_t)((uint64_t)stride_ * (gh_ - 1) + 3ull * gw_),
-        0x00020000);
+    const RgbRsrc rgb_rs = rgb_rsrc(rgb_, stride_, ps_, gw_, gh_);
     const __amdgpu_buffer_rsrc_t coef_rs =
         __builtin_amdgcn_make_buffer_rsrc(a.coef, 0, (int)(uint32_t)((uint64_t)a.g.nblocks() * 128), 0x00020000);
 
@@ -210,21 +309,19 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         return __builtin_amdgcn_readfirstlane(v);
     };
 
-    // 48-byte RGB run of this lane for partition tile k, if the tile is on the aligned
-    // fast path (else zeros, and the staging takes the clamped edge path)
+    // the pixel run of this lane (48 bytes of RGB8) for partition tile k, if the tile is on the
+    // aligned fast path (else zeros, and the staging takes the clamped edge path)
     // (tile numbers are wave-uniform: the tile's row and column come from scalar
     // arithmetic, and only this lane's fixed offset within the tile is per lane)
-    const uint32_t lane_off = (uint32_t)r16 * (uint32_t)stride_ + (uint32_t)c16 * 48u;
-    auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2) -> bool {
+    const uint32_t lane_off = (uint32_t)r16 * (uint32_t)stride_ + (uint32_t)c16 * kRun;
+    auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * 4;
         const uint32_t y = mrow * 16 + r16, xs = mcol0 * 16 + c16 * 16;
         const bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
-        const uint32_t base = (uint32_t)((uint64_t)(mrow * 16) * stride_ + (uint64_t)mcol0 * 48);  // (uniform)
+        const uint32_t base = (uint32_t)((uint64_t)(mrow * 16) * stride_ + (uint64_t)mcol0 * kRun);  // (uniform)
         const uint32_t off = ok ? base + lane_off : kOob;
-        v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rgb_rs, off, 0, 0));
-        v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rgb_rs, off + 16, 0, 0));
-        v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rgb_rs, off + 32, 0, 0));
+        load_run(rgb_rs, off, v0, v1, v2, v3);
         return ok;
     };
     // The last round's 16-byte coefficient row (kOob: none) is stored during the
@@ -234,8 +331,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     uint32_t poff = kOob;
     auto store_pending = [&] { __builtin_amdgcn_raw_buffer_store_b128(pend, coef_rs, poff, 0, kK1StoreAux); };
     uint32_t k = __builtin_amdgcn_readfirstlane((uint32_t)wv);  // this wave's current tile of the run
-    uint4 c0, c1, c2;
-    bool cfast = fast_load(k, c0, c1, c2);  // issued before the prologue's own memory traffic
+    uint4 c0, c1, c2, c3;
+    bool cfast = fast_load(k, c0, c1, c2, c3);  // issued before the prologue's own memory traffic
 
     for (uint32_t i = bid * kK1Threads + tid; i < a.zero_words; i += nbk * kK1Threads) a.zero[i] = 0;
     if (bid == 0)  // carried: another frame's tables + headers, host -> device
@@ -362,24 +459,22 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         // (the prefetched registers are consumed on every path, so no later wait on
         // them can also drain the previous tile's coefficient stores)
         uint32_t px[16];
-        {
+        if constexpr (kShape == kShapeX4 || kShape == kShapePlanar) {
+            unpack_run(c0, c1, c2, c3, sel4_, px);
+        } else {
             const uint4 v0 = c0, v1 = c1, v2 = c2;
             const uint32_t wd[13] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, 0u};
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int b0 = 3 * i, d = b0 >> 2, sh = 8 * (b0 & 3);
-                // bytes b0..b0+2 of the run, zero-extended (perm selector 0x0c = 0x00)
-                const uint32_t o8 = (uint32_t)(sh / 8);
-                px[i] = __builtin_amdgcn_perm(wd[d + 1], wd[d], 0x0C000000u | ((o8 + 2) << 16) | ((o8 + 1) << 8) | o8);
+                const int b0 = 3 * i, d = b0 >> 2;
+                // bytes b0..b0+2 of the run, zero-extended (perm selector 0x0c = 0x00); BGR8: 2, 1, 0
+                const uint32_t o8 = (uint32_t)(b0 & 3);
+                px[i] = __builtin_amdgcn_perm(wd[d + 1], wd[d], sel3(o8));
             }
         }
         if (!cfast) {  // right/bottom edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            for (int i = 0; i < 16; ++i) {
-                const uint32_t sx = min(xs + i, gw_ - 1);
-                const uint8_t* p = rgb_ + (uint64_t)sy * stride_ + (uint64_t)sx * 3;
-                px[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-            }
+            for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
         uint32_t* dst = &W.rgbx[r16 * kRgbPitch + c16 * 16];
 #pragma unroll
@@ -388,7 +483,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         // prefetch the next tile of this wave (into the registers just staged) while
         // this one is transformed
         store_pending();
-        cfast = fast_load(kn, c0, c1, c2);
+        cfast = fast_load(kn, c0, c1, c2, c3);
         const uint32_t kn2 = kn < n_p ? grab() : n_p;
 
         // ---- rounds: Cb x4 + Cr x4, Y blocks 0-7 (MCUs 0, 1), Y blocks 8-15 (MCUs 2, 3) ----
@@ -479,6 +574,16 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     uint64_t stride_ = a.stride;
     uint32_t gw_ = a.g.width, gh_ = a.g.height;
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
+    uint64_t ps_ = 0;                // planar: the plane pitch
+    uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
+    if constexpr (kShape == kShapePlanar) {
+        ps_ = a.plane_stride;
+        asm volatile("" : "+s"(ps_));
+    }
+    if constexpr (kShape == kShapeX4) {
+        sel4_ = a.fmt == kFmtBgra8 ? kSelBgrx : kSelRgbx;
+        asm volatile("" : "+s"(sel4_));
+    }
     constexpr int kK1Threads = kWaves * 64;
     constexpr uint32_t kMcus = 16 / kYh;            // MCUs per tile
     constexpr int kBpm = kYh + 2;                   // blocks per MCU
@@ -491,13 +596,11 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     const uint32_t tiles_per_row = (mw + kMcus - 1) / kMcus;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    const bool aligned = (((uintptr_t)rgb_ | stride_) & 15) == 0;
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0;
     const int r8 = lane >> 3, c8 = lane & 7;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;   // DCT: lane -> (block of the round, column)
 
-    const __amdgpu_buffer_rsrc_t rgb_rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(rgb_), 0, (int)(uint32_t)((uint64_t)stride_ * (gh_ - 1) + 3ull * gw_),
-        0x00020000);
+    const RgbRsrc rgb_rs = rgb_rsrc(rgb_, stride_, ps_, gw_, gh_);
     const __amdgpu_buffer_rsrc_t coef_rs =
         __builtin_amdgcn_make_buffer_rsrc(a.coef, 0, (int)(uint32_t)((uint64_t)a.g.nblocks() * 128), 0x00020000);
 
@@ -509,25 +612,23 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         if (lane == 0) v = atomicAdd(&lds.next, 1u);
         return __builtin_amdgcn_readfirstlane(v);
     };
-    const uint32_t lane_off = (uint32_t)r8 * (uint32_t)stride_ + (uint32_t)c8 * 48u;  // (as in fdct_kernel)
-    auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2) -> bool {
+    const uint32_t lane_off = (uint32_t)r8 * (uint32_t)stride_ + (uint32_t)c8 * kRun;  // (as in fdct_kernel)
+    auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * kMcus;
         const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
         const bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
-        const uint32_t base = (uint32_t)((uint64_t)(mrow * 8) * stride_ + (uint64_t)mcol0 * 24 * kYh);  // (uniform)
+        const uint32_t base = (uint32_t)((uint64_t)(mrow * 8) * stride_ + (uint64_t)mcol0 * (kRun / 2) * kYh);  // (uniform)
         const uint32_t off = ok ? base + lane_off : kOob;
-        v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rgb_rs, off, 0, 0));
-        v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rgb_rs, off + 16, 0, 0));
-        v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rgb_rs, off + 32, 0, 0));
+        load_run(rgb_rs, off, v0, v1, v2, v3);
         return ok;
     };
     u32x4 pend;
     uint32_t poff = kOob;
     auto store_pending = [&] { __builtin_amdgcn_raw_buffer_store_b128(pend, coef_rs, poff, 0, kK1StoreAux); };
     uint32_t k = __builtin_amdgcn_readfirstlane((uint32_t)wv);
-    uint4 c0, c1, c2;
-    bool cfast = fast_load(k, c0, c1, c2);
+    uint4 c0, c1, c2, c3;
+    bool cfast = fast_load(k, c0, c1, c2, c3);
 
     for (uint32_t i = bid * kK1Threads + tid; i < a.zero_words; i += nbk * kK1Threads) a.zero[i] = 0;
     if (bid == 0)
@@ -567,30 +668,29 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
 
         uint32_t px[16];
-        {
+        if constexpr (kShape == kShapeX4 || kShape == kShapePlanar) {
+            unpack_run(c0, c1, c2, c3, sel4_, px);
+        } else {
             const uint4 v0 = c0, v1 = c1, v2 = c2;
             const uint32_t wd[13] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, 0u};
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int b0 = 3 * i, d = b0 >> 2;
+                // bytes b0..b0+2 of the run, zero-extended (perm selector 0x0c = 0x00); BGR8: 2, 1, 0
                 const uint32_t o8 = (uint32_t)(b0 & 3);
-                px[i] = __builtin_amdgcn_perm(wd[d + 1], wd[d], 0x0C000000u | ((o8 + 2) << 16) | ((o8 + 1) << 8) | o8);
+                px[i] = __builtin_amdgcn_perm(wd[d + 1], wd[d], sel3(o8));
             }
         }
         if (!cfast) {  // edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            for (int i = 0; i < 16; ++i) {
-                const uint32_t sx = min(xs + i, gw_ - 1);
-                const uint8_t* p = rgb_ + (uint64_t)sy * stride_ + (uint64_t)sx * 3;
-                px[i] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-            }
+            for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
         uint32_t* dst = &W.rgbx[r8 * kRgbPitch444 + c8 * 16];
 #pragma unroll
         for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
         wave_order();
         store_pending();
-        cfast = fast_load(kn, c0, c1, c2);
+        cfast = fast_load(kn, c0, c1, c2, c3);
         const uint32_t kn2 = kn < n_p ? grab() : n_p;
 
         uint32_t p[8];
@@ -664,14 +764,19 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
 // (262 144 tiles), where the whole-CU workgroups' shared tile counter balances ~64
 // tiles per wave.
 constexpr uint32_t kK1WholeCuTiles = 65536;
+uint32_t k1_tiles(const Geometry& g);
+bool k1_whole_cu(const Geometry& g, bool solo);
+#if JPGE_K1_SHAPE == 0
 uint32_t k1_tiles(const Geometry& g) {
     const uint32_t per = g.row8() ? 16 / g.yh : 4;  // MCUs per tile
     return ((g.mw + per - 1) / per) * g.mh;
 }
 bool k1_whole_cu(const Geometry& g, bool solo) { return solo && k1_tiles(g) >= kK1WholeCuTiles; }
+#endif
 
+// (static, like the kernels: every load shape's build has its own)
 template <int kYh, int kN>
-hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
+static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     const FdctArgs& a = fs.a[0];
     const bool ex = a.maxval == 255;
     if (k1_whole_cu(a.g, a.solo)) {
@@ -684,7 +789,7 @@ hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStrea
 }
 
 template <int kFilt, int kN>
-hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
+static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     const FdctArgs& a = fs.a[0];
     const bool ex = a.maxval == 255;
     if (k1_whole_cu(a.g, a.solo)) {
@@ -695,6 +800,39 @@ hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream
         else return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     }
 }
+
+// This build's kernel for a validated set (launch_fdct_fs) of grid workgroups.
+template <int kN>
+static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
+    const FdctArgs& a = fs.a[0];
+    // the kernels assume these shapes (kernels.hpp Geometry)
+    if (a.g.row8()) {
+        switch (a.g.yh) {
+            // (launch_timed returns the launch's error: hipGetLastError has already consumed it)
+            case 1: return a.g.bpm != 3 ? hipErrorInvalidValue : launch_row8<1, kN>(fs, grid, s, t);
+            case 2: return a.g.bpm != 4 ? hipErrorInvalidValue : launch_row8<2, kN>(fs, grid, s, t);
+            case 4: return a.g.bpm != 6 ? hipErrorInvalidValue : launch_row8<4, kN>(fs, grid, s, t);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    if (a.g.yh != 2 || a.g.bpm != 6) return hipErrorInvalidValue;
+    switch (a.g.cfilt) {
+        case kFiltS420m: return launch_420<kFiltS420m, kN>(fs, grid, s, t);
+        case kFiltS420lm: return launch_420<kFiltS420lm, kN>(fs, grid, s, t);
+        case kFiltS420: return launch_420<kFiltS420, kN>(fs, grid, s, t);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+#if JPGE_K1_SHAPE != 0
+// this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar)
+hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
+    return launch_k1<kMaxSet>(fs, grid, s, t);
+}
+#else
+hipError_t launch_fdct_bgr8(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_x4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_planar(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 
 uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs) {
     const uint32_t tiles = k1_tiles(g);
@@ -717,28 +855,29 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         const FdctArgs& m = fs.a[f];
         // 32-bit buffer offsets: the frame's pixels and coefficients must stay below kOob
         // (a 16384^2 frame needs 805 MB of each)
-        if ((uint64_t)m.stride * m.g.height >= kOob || (uint64_t)m.g.nblocks() * 128 >= kOob) return hipErrorInvalidValue;
+        // (planar: each plane has its own descriptor, so the extent is one plane's)
+        if (m.fmt < 0 || m.fmt >= kFmtCount || m.g.height == 0) return hipErrorInvalidValue;
+        const uint64_t row = (uint64_t)fmt_bpp(m.fmt) * m.g.width;
+        const uint64_t extent = m.stride * (m.g.height - 1) + row;  // the descriptor's range
+        if (m.stride < row || extent >= kOob || (uint64_t)m.stride * m.g.height >= kOob ||
+            (uint64_t)m.g.nblocks() * 128 >= kOob)
+            return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
+            fmt_shape(m.fmt) != fmt_shape(a.fmt) ||
             m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs))
             return hipErrorInvalidValue;
     }
     const uint32_t grid = fs.wg0[fs.n];
-    // the kernels assume these shapes (kernels.hpp Geometry)
-    if (a.g.row8()) {
-        switch (a.g.yh) {
-            // (launch_timed returns the launch's error: hipGetLastError has already consumed it)
-            case 1: return a.g.bpm != 3 ? hipErrorInvalidValue : launch_row8<1, kN>(fs, grid, s, t);
-            case 2: return a.g.bpm != 4 ? hipErrorInvalidValue : launch_row8<2, kN>(fs, grid, s, t);
-            case 4: return a.g.bpm != 6 ? hipErrorInvalidValue : launch_row8<4, kN>(fs, grid, s, t);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    if (a.g.yh != 2 || a.g.bpm != 6) return hipErrorInvalidValue;
-    switch (a.g.cfilt) {
-        case kFiltS420m: return launch_420<kFiltS420m, kN>(fs, grid, s, t);
-        case kFiltS420lm: return launch_420<kFiltS420lm, kN>(fs, grid, s, t);
-        case kFiltS420: return launch_420<kFiltS420, kN>(fs, grid, s, t);
-        default: return hipErrorInvalidValue;
+    if (fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
+    // the other load shapes have the frame-set instance only (a lone frame is a set of one)
+    FrameSet<FdctArgs, kMaxSet> w{};
+    w.n = fs.n;
+    for (uint32_t f = 0; f < fs.n; ++f) w.a[f] = fs.a[f];
+    for (uint32_t f = 0; f <= fs.n; ++f) w.wg0[f] = fs.wg0[f];
+    switch (fmt_shape(a.fmt)) {
+        case kShapeBgr8: return launch_fdct_bgr8(w, grid, s, t);
+        case kShapeX4: return launch_fdct_x4(w, grid, s, t);
+        default: return launch_fdct_planar(w, grid, s, t);
     }
 }
 
@@ -750,5 +889,6 @@ hipError_t launch_fdct_set(const FdctArgs* a, int n, hipStream_t s, const KTimer
     if (n < 1 || n > kMaxSet) return hipErrorInvalidValue;
     return launch_fdct_fs(frame_set(a, n, fdct_grid(a[0].g, a[0].solo, a[0].wgs)), s, t);
 }
+#endif  // JPGE_K1_SHAPE == 0
 
 }  // namespace jpge

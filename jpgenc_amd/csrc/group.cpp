@@ -281,6 +281,11 @@ int jpge_group_encode_striped(jpge_group* g, const uint8_t* rgb, uint32_t width,
         return (int)JPGE_E_ARG;
     std::lock_guard<std::mutex> lk(g->mu);
     const int N = (int)g->ctx.size();
+    for (auto* c : g->ctx) {  // the striped entry reads interleaved RGB8 only
+        int fmt = JPGE_FMT_RGB8;
+        if (const int st = jpge_get_input_format(c, &fmt, nullptr)) return st;
+        if (fmt != JPGE_FMT_RGB8) return (int)JPGE_E_ARG;
+    }
     const size_t row = (size_t)width * 3, pitch = stride ? stride : row;
     if (pitch < row) return (int)JPGE_E_ARG;
     // stripes of whole MCU rows; with restart intervals every stripe starts one

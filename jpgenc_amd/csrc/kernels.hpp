@@ -3,7 +3,8 @@
 // geometry.
 //
 // Data layout in HBM (per frame):
-//   rgb   : interleaved RGB8, row pitch `stride` (16-byte aligned pitch/base = fast path)
+//   rgb   : the frame's pixels in one of the input layouts below, row pitch `stride`
+//           (16-byte aligned pitch/base/plane pitch = fast path)
 //   coef  : int16 [nmcu][6][64]  quantised coefficients, NATURAL order inside a block,
 //           blocks in MCU-interleave order Y00 Y01 Y10 Y11 Cb Cr (= entropy order)
 //   hist  : u32 cnt[kHistReplicas][4][256], u64 key[4][256] (~first-occurrence key)
@@ -46,6 +47,20 @@ struct Geometry {
 // component of MCU slot k: 0 = Y, 1 = Cb, 2 = Cr (the last two slots are the chroma)
 JPGE_HD inline int block_comp(int k, uint32_t bpm) { return k < (int)bpm - 2 ? 0 : k - ((int)bpm - 3); }
 
+// Input layouts (jpge.h JPGE_FMT_*, the same values) and K1's load shapes: what a lane
+// loads for its 16-pixel run.  Each shape is one build of fdct.hip (JPGE_K1_SHAPE).
+constexpr int kFmtRgb8 = 0, kFmtBgr8 = 1, kFmtRgba8 = 2, kFmtBgra8 = 3, kFmtRgb8Planar = 4, kFmtCount = 5;
+constexpr int kShapeRgb8 = 0;    // 48 bytes R,G,B,...: three b128 loads
+constexpr int kShapeBgr8 = 1;    // the same loads, bytes 2,1,0 of each pixel
+constexpr int kShapeX4 = 2;      // RGBA8 / BGRA8: 64 bytes, four b128 loads, a wave-uniform byte selector
+constexpr int kShapePlanar = 3;  // 16 bytes of each of the planes R, G, B: three b128 loads
+JPGE_HD inline int fmt_shape(int fmt) {
+    return fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar : kShapeX4;
+}
+// bytes per pixel within a row (planar: of one plane), and planes
+JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtRgb8Planar ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
+JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt == kFmtRgb8Planar ? 3u : 1u; }
+
 constexpr int kHistReplicas = 8;  // spread of the global histogram atomics
 constexpr int kStatsTile = 128;           // blocks per statistics tile (4 lanes each)
 constexpr int kEntropyTile = 128;         // blocks per entropy tile (4 lanes each)
@@ -79,6 +94,9 @@ struct FdctArgs {
     uint4* imp_dst;
     uint32_t imp_n16;
     uint64_t* dbg;   // diagnostic phase stamps (JPGE_STAMPS builds), else unused
+    // input layout (kFmt*); planar: plane c's rows start at rgb + c * plane_stride
+    int fmt = kFmtRgb8;
+    uint64_t plane_stride = 0;
 };
 
 // Stripe context of a frame (a row stripe of a larger image); the

@@ -135,20 +135,40 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
 #define JPGE_FMT_BGRA8 3       /* interleaved B,G,R,A; alpha ignored */
 #define JPGE_FMT_RGB8_PLANAR 4 /* planes R, G, B of `height` rows of `stride` bytes, 1 byte per
                                   pixel, at rgb, rgb + plane_stride, rgb + 2*plane_stride */
+/* Frames of full-range (JFIF) 8-bit Y, Cb, Cr samples, a video decoder's output: no
+ * colour conversion runs, a sample v enters the transform as the value v - 128 (the
+ * reference Image's plane after convertToColorSpace(YCbCr)).  `rgb` points at the Y
+ * plane and `stride` is its row pitch; maxval must be 255 (else JPGE_E_ARG, in a batch
+ * the frame's status).  With cw = ceil(width / 2), ch = ceil(height / 2):
+ *   NV12: the Cb,Cr plane at rgb + plane_stride (0 = stride * height), ch rows of pitch
+ *     `stride`, Cb at even bytes and Cr at odd bytes; stride 0 = width rounded up to even.
+ *   I420: the Cb plane at rgb + plane_stride (0 = stride * height), ch rows of pitch
+ *     cs = (stride + 1) / 2; the Cr plane at Cb + cs * ch; stride 0 = width.
+ *   YUV444_PLANAR: addressed exactly as JPGE_FMT_RGB8_PLANAR; the context's subsampling
+ *     mode (any of the six) filters Cb and Cr as it does after a colour conversion.
+ * NV12 and I420 chroma is subsampled already: the planes are taken as the output of the
+ * 4:2:0 averaging (Y edge-replicated to whole 16x16 MCUs, each chroma plane
+ * edge-replicated, in the chroma domain, to half that), and the context must be in
+ * JPGE_S420_M (the default): in another mode the encode calls return JPGE_E_ARG.  The
+ * fast path needs every plane's base and pitch 16-byte aligned (I420: a stride that is
+ * a multiple of 32). */
+#define JPGE_FMT_NV12 16
+#define JPGE_FMT_I420 17
+#define JPGE_FMT_YUV444_PLANAR 18
 
 /* Input layout for the context's following jpge_encode_rgb8, jpge_encode_batch,
  * jpge_fdct_quant and jpge_symbol_stats calls (their `rgb` then points at a frame in
  * that layout), also on a group member's context (jpge_group_context), and so for
- * jpge_group_encode_batch.  plane_stride: the planar layout's bytes between planes,
- * 0 = stride * height of each frame (contiguous CHW); non-zero with an interleaved
- * layout, or an unknown layout: JPGE_E_ARG.  A frame's stride of 0 means width * the
+ * jpge_group_encode_batch.  plane_stride: the planar layouts' bytes between planes
+ * (NV12, I420: from the Y plane to the chroma), 0 = stride * height of each frame
+ * (contiguous CHW); non-zero with an interleaved layout, or an unknown layout: JPGE_E_ARG.  A frame's stride of 0 means width * the
  * layout's bytes per pixel (planar: width); a smaller stride is JPGE_E_ARG.  maxval
  * scales the three colour channels as before.  The fast path needs the pointer, the
  * stride and the plane stride 16-byte aligned; anything else works, slower.
  * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
  * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
  * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
- * the planar one; jpge_group_encode_striped needs JPGE_FMT_RGB8. */
+ * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
 int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
 /* the current setting (plane_stride may be NULL) */
 int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride);

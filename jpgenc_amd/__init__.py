@@ -26,6 +26,10 @@ JPGE_DEVICE_OUTPUT = 2
 
 #: input layouts (jpge.h JPGE_FMT_*): interleaved (H, W, 3) / (H, W, 4) frames, or planar (3, H, W)
 JPGE_FMT_RGB8, JPGE_FMT_BGR8, JPGE_FMT_RGBA8, JPGE_FMT_BGRA8, JPGE_FMT_RGB8_PLANAR = 0, 1, 2, 3, 4
+#: full-range 8-bit Y, Cb, Cr frames (no colour conversion): NV12 and I420 (chroma at half size;
+#: host frames from pack_yuv420), and planar (3, H, W)
+JPGE_FMT_NV12, JPGE_FMT_I420, JPGE_FMT_YUV444_PLANAR = 16, 17, 18
+_FMT_420 = (JPGE_FMT_NV12, JPGE_FMT_I420)
 
 #: subsampling modes (jpge.h JPGE_S*) -> (Y blocks across, Y blocks down) an MCU
 SUBSAMPLING = {420: (2, 2), 4200: (2, 2), 4201: (2, 2), 444: (1, 1), 422: (2, 1), 411: (4, 1)}
@@ -399,15 +403,83 @@ def input_format_info(fmt: int) -> tuple[int, int]:
     return b.value, n.value
 
 
+class Yuv420Frame(np.ndarray):
+    """A host NV12 or I420 frame (pack_yuv420): the layout's bytes, planes back to back
+    (plane stride 0), with the geometry that a flat buffer does not show."""
+    fmt = width = height = stride = None
+
+    def __array_finalize__(self, obj):
+        for k in ("fmt", "width", "height", "stride"):
+            setattr(self, k, getattr(obj, k, None))
+
+
+def yuv420_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of an NV12 or I420 frame with plane stride 0 (stride 0: the least one)."""
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    if fmt == JPGE_FMT_NV12:
+        return (stride or 2 * cw) * (h + ch)
+    if fmt == JPGE_FMT_I420:
+        stride = stride or w
+        return stride * h + 2 * ((stride + 1) // 2) * ch
+    raise ValueError(f"input layout {fmt} is not a 4:2:0 one")
+
+
+def pack_yuv420(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
+    """(frame, w, h, stride): the (H, W) Y plane and the (ceil(H/2), ceil(W/2)) Cb and Cr planes
+    as one contiguous host frame in layout JPGE_FMT_NV12 or JPGE_FMT_I420 with the least
+    stride and plane stride 0 (jpge.h).  The frame (a Yuv420Frame) is what encode,
+    encode_batch, fdct_quant and symbol_stats take when the input layout is `fmt`."""
+    y, cb, cr = (np.ascontiguousarray(p, np.uint8) for p in (y, cb, cr))
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
+    h, w = y.shape
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    if cb.shape != (ch, cw) or cr.shape != (ch, cw):
+        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({ch}, {cw}) for a {w}x{h} frame")
+    if fmt == JPGE_FMT_NV12:
+        stride = 2 * cw
+        buf = np.zeros((h + ch, stride), np.uint8)  # (odd width: one pad byte per Y row)
+        buf[:h, :w] = y
+        buf[h:, 0::2] = cb
+        buf[h:, 1::2] = cr
+        buf = buf.reshape(-1)
+    elif fmt == JPGE_FMT_I420:
+        stride = w  # chroma pitch (w + 1) / 2 = cw
+        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
+    else:
+        raise ValueError(f"input layout {fmt} is not a 4:2:0 one")
+    f = buf.view(Yuv420Frame)
+    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
+    return f, w, h, stride
+
+
 def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     """(width, height, row stride in bytes) of a C-contiguous frame shaped for layout `fmt`:
-    (H, W, 3), (H, W, 4) or (3, H, W)."""
+    (H, W, 3), (H, W, 4) or (3, H, W); NV12 and I420: a pack_yuv420 frame of that layout."""
     bpp, planes = input_format_info(fmt)
+    if fmt in _FMT_420:
+        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
+                a.size != yuv420_bytes(fmt, a.width, a.height, a.stride):
+            raise ValueError(f"input layout {fmt} takes a pack_yuv420({fmt}, y, cb, cr) frame")
+        return a.width, a.height, a.stride
     want = "(3, H, W)" if planes == 3 else f"(H, W, {bpp})"
     if a.ndim != 3 or (a.shape[0] != 3 if planes == 3 else a.shape[2] != bpp):
         raise ValueError(f"frame of shape {a.shape}: input layout {fmt} takes {want}")
     h, w = (a.shape[1], a.shape[2]) if planes == 3 else (a.shape[0], a.shape[1])
     return w, h, w * bpp
+
+
+def _as_frame(a, fmt: int):
+    """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
+    if fmt not in _FMT_420:
+        a = np.ascontiguousarray(a, np.uint8)
+    w, h, stride = _frame_geom(a, fmt)
+    return np.ascontiguousarray(a, np.uint8), w, h, stride
+
+
+def _as_frames(frames, fmt: int):
+    fr = [_as_frame(f, fmt) for f in frames]
+    return [f[0] for f in fr], [f[1:] for f in fr]
 
 
 def device_count() -> int:
@@ -498,8 +570,9 @@ class Encoder:
 
     def set_input_format(self, fmt: int, plane_stride: int = 0) -> None:
         """Input layout of the following encodes (JPGE_FMT_*): frames are then (H, W, 3),
-        (H, W, 4) or, planar, (3, H, W).  plane_stride: bytes between the planes of the
-        raw-pointer entries' planar frames (0 = stride * height)."""
+        (H, W, 4) or, planar, (3, H, W); NV12 and I420: pack_yuv420 frames.  plane_stride:
+        bytes between the planes of the raw-pointer entries' planar frames (NV12, I420: from
+        the Y plane to the chroma; 0 = stride * height)."""
         _check(lib().jpge_set_input_format(self._ctx, int(fmt), int(plane_stride)), "set_input_format")
         self._fmt = int(fmt)
 
@@ -523,8 +596,7 @@ class Encoder:
     def encode(self, rgb: np.ndarray, quality: int = 50, maxval: int = 255, qy=None, qc=None) -> bytes:
         """Image::writeJPEG (Image.cpp:831-976) on an (H, W, 3) uint8 frame -> .jpg bytes
         (the frame shaped for the input layout, set_input_format)."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        w, h, stride = _frame_geom(rgb, self._fmt)
+        rgb, w, h, stride = _as_frame(rgb, self._fmt)
         qy, qc = self._tables(quality, qy, qc)
         out = np.empty(max_jpeg_bytes(w, h), np.uint8)
         n = ctypes.c_size_t()
@@ -601,6 +673,91 @@ class Encoder:
             self.set_input_format(*prev)
         return n if host_out is None else host_out[:n].tobytes()
 
+    def encode_tensor_yuv(self, y, cbcr_or_cb, cr=None, quality: int = 50, out=None):
+        """One frame of full-range Y, Cb, Cr torch uint8 tensors (a decoder's surface) through
+        jpge_encode_rgb8, read in place: (H, W) + (ch, cw, 2) is NV12, (H, W) + two (ch, cw) is
+        I420, (H, W) + two (H, W) is YUV444_PLANAR (ch, cw: H, W halved, rounded up).  The
+        planes must be views of one allocation, all on one device, at offsets the layout can
+        express (jpge.h): unit inner strides, the chroma after the Y plane, NV12's Cb,Cr rows
+        at the Y pitch, I420's Cb and Cr rows at pitch (Y pitch + 1) / 2 with Cr ch rows after
+        Cb, the 4:4:4 planes at the Y pitch and equally spaced; else ValueError.  A 4:2:0
+        layout needs subsampling mode 420.  Returns the .jpg bytes, or, with `out` a uint8
+        tensor on the frame's device, writes them there and returns their length.  The
+        encoder's input layout is the same afterwards."""
+        planes = [y, cbcr_or_cb] + ([] if cr is None else [cr])
+        for p in planes:
+            if p.element_size() != 1 or p.dtype.is_floating_point or p.device != y.device:
+                raise ValueError("encode_tensor_yuv takes uint8 tensors on one device")
+        if y.dim() != 2 or y.numel() == 0:
+            raise ValueError(f"Y plane of shape {tuple(y.shape)}: (H, W)")
+        h, w = y.shape
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        c = cbcr_or_cb
+        if cr is None and tuple(c.shape) == (ch, cw, 2):
+            fmt = JPGE_FMT_NV12
+        elif cr is not None and tuple(c.shape) == (ch, cw) == tuple(cr.shape) and (h, w) != (ch, cw):
+            fmt = JPGE_FMT_I420
+        elif cr is not None and tuple(c.shape) == (h, w) == tuple(cr.shape):
+            fmt = JPGE_FMT_YUV444_PLANAR  # (a 1x1 frame's planes fit both: the layouts agree on it)
+        else:
+            raise ValueError(f"chroma of shape {tuple(c.shape)}" + ("" if cr is None else f", {tuple(cr.shape)}") +
+                             f" for a {w}x{h} Y plane: ({ch}, {cw}, 2), two ({ch}, {cw}) or two ({h}, {w})")
+        store = y.untyped_storage().data_ptr()
+        if any(p.untyped_storage().data_ptr() != store for p in planes):
+            raise ValueError("the planes must be views of one allocation")
+        def pitch(p):  # a plane's row pitch (None: one row, any pitch)
+            if p.stride(1) != 1 and p.shape[1] > 1:
+                raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
+            return p.stride(0) if p.shape[0] > 1 else None
+        stride = pitch(y)
+        plane_stride = c.data_ptr() - y.data_ptr()
+        if plane_stride <= 0:
+            raise ValueError("the chroma must follow the Y plane in memory")
+        if fmt == JPGE_FMT_NV12:
+            if c.stride(2) != 1 or (c.stride(1) != 2 and cw > 1):
+                raise ValueError(f"strides {tuple(c.stride())}: Cb,Cr pairs must be packed")
+            cp = c.stride(0) if ch > 1 else None
+            stride = stride if stride is not None else cp if cp is not None else 2 * cw
+            if cp is not None and cp != stride:
+                raise ValueError(f"chroma pitch {cp}: NV12's Cb,Cr rows have the Y pitch {stride}")
+            least = 2 * cw
+        elif fmt == JPGE_FMT_I420:
+            cp, rp = pitch(c), pitch(cr)
+            if stride is None:  # (one Y row: any pitch whose half is the chroma's)
+                stride = 2 * cp if cp is not None else 2 * rp if rp is not None else w
+            cs = (stride + 1) // 2
+            if any(q is not None and q != cs for q in (cp, rp)):
+                raise ValueError(f"chroma pitches {cp}, {rp}: I420's are (Y pitch + 1) / 2 = {cs}")
+            if cr.data_ptr() - c.data_ptr() != cs * ch:
+                raise ValueError(f"the Cr plane must start {cs * ch} bytes ({ch} rows) after the Cb plane")
+            least = w
+        else:
+            cp, rp = pitch(c), pitch(cr)
+            stride = next((q for q in (stride, cp, rp) if q is not None), w)
+            if any(q is not None and q != stride for q in (cp, rp)):
+                raise ValueError(f"chroma pitches {cp}, {rp}: the planes share the Y pitch {stride}")
+            if cr.data_ptr() - c.data_ptr() != plane_stride:
+                raise ValueError("the Y, Cb and Cr planes must be equally spaced")
+            least = w
+        if stride < least:
+            raise ValueError("rows overlap")
+        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
+        host_out = None
+        if out is None:
+            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            out_ptr, cap = _p(host_out), host_out.size
+        else:
+            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out: a contiguous uint8 device tensor")
+            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
+        prev = self.input_format()
+        self.set_input_format(fmt, plane_stride)
+        try:
+            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
+        finally:
+            self.set_input_format(*prev)
+        return n if host_out is None else host_out[:n].tobytes()
+
     def encode_batch_dev(self, frames: list[tuple[int, int, int, int]], outs: list[tuple[int, int]],
                          quality: int = 50, maxval: int = 255,
                          flags: int = JPGE_DEVICE_INPUT | JPGE_DEVICE_OUTPUT) -> list[int]:
@@ -626,8 +783,7 @@ class Encoder:
 
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         qy, qc = self._tables(quality, None, None)
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-        geom = [_frame_geom(f, self._fmt) for f in frames]
+        frames, geom = _as_frames(frames, self._fmt)
         outs = [np.empty(max_jpeg_bytes(w, h), np.uint8) for w, h, _ in geom]
         arr = (Frame * len(frames))()
         for i, (f, o, (w, h, stride)) in enumerate(zip(frames, outs, geom)):
@@ -639,8 +795,7 @@ class Encoder:
     def fdct_quant(self, rgb: np.ndarray, quality: int = 50, maxval: int = 255, qy=None, qc=None):
         """Stage dump: quantised coefficients (before DC diff) -> (Y, Cb, Cr) arrays of shape
         (nblocks, 64), blocks in raster order, natural order within a block."""
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        w, h, stride = _frame_geom(rgb, self._fmt)
+        rgb, w, h, stride = _as_frame(rgb, self._fmt)
         yh, yv = SUBSAMPLING[getattr(self, "_sub", 420)]
         mw, mh = -(-w // (8 * yh)), -(-h // (8 * yv))  # MCUs across / down
         y = np.zeros((mw * yh * mh * yv, 64), np.int16)
@@ -752,8 +907,7 @@ class Encoder:
         return [int(x) for x in lens]
 
     def symbol_stats(self, rgb: np.ndarray, quality: int = 50, maxval: int = 255):
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        w, h, stride = _frame_geom(rgb, self._fmt)
+        rgb, w, h, stride = _as_frame(rgb, self._fmt)
         qy, qc = self._tables(quality, None, None)
         counts = np.zeros(1024, np.uint32)
         first = np.zeros(1024, np.uint64)
@@ -805,8 +959,7 @@ class Group:
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         """Config 4: frame i on member i mod N."""
         qy, qc = quality_tables(quality)
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-        geom = [_frame_geom(f, self._fmt) for f in frames]
+        frames, geom = _as_frames(frames, self._fmt)
         outs = [np.empty(max_jpeg_bytes(w, h), np.uint8) for w, h, _ in geom]
         arr = (Frame * len(frames))()
         for i, (f, o, (w, h, stride)) in enumerate(zip(frames, outs, geom)):

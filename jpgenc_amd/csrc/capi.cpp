@@ -180,7 +180,7 @@ const char* jpge_strerror(int s) {
     }
 }
 
-int jpge_version(void) { return 101; }
+int jpge_version(void) { return 102; }
 
 int jpge_device_count(int* n) {
     if (!n) return JPGE_E_ARG;
@@ -280,7 +280,7 @@ int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride) {
 }
 
 int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes) {
-    if (format < 0 || format >= jpge::kFmtCount) return JPGE_E_ARG;
+    if (!jpge::fmt_valid(format)) return JPGE_E_ARG;
     if (bytes_per_pixel) *bytes_per_pixel = (int)jpge::fmt_bpp(format);
     if (planes) *planes = (int)jpge::fmt_planes(format);
     return JPGE_OK;

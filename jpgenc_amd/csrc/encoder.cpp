@@ -423,8 +423,8 @@ int Encoder::set_restart(uint32_t mcus) {
 }
 
 int Encoder::set_input_format(int fmt, size_t plane_stride) {
-    if (fmt < 0 || fmt >= kFmtCount) return kErrArg;
-    if (plane_stride && fmt != kFmtRgb8Planar) return kErrArg;
+    if (!fmt_valid(fmt)) return kErrArg;
+    if (plane_stride && fmt_planes(fmt) == 1) return kErrArg;
     fmt_ = fmt;
     plane_stride_ = plane_stride;
     return kOk;
@@ -772,14 +772,23 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     if (!f.rgb || f.width == 0 || f.height == 0 || f.width > 65535 || f.height > 65535) return kErrArg;
     if (f.maxval < 1 || f.maxval > 255) return kErrRange;
     const Geometry g = geometry(f.width, f.height, mode_);
-    if (f.fmt < 0 || f.fmt >= kFmtCount || (f.plane_stride && f.fmt != kFmtRgb8Planar)) return kErrArg;
-    const size_t row = (size_t)f.width * fmt_bpp(f.fmt);
+    if (!fmt_valid(f.fmt) || (f.plane_stride && fmt_planes(f.fmt) == 1)) return kErrArg;
+    // Y, Cb, Cr samples are 8-bit, and half-size chroma planes are the S420_m mode's planes
+    if (fmt_yuv(f.fmt) && (f.maxval != 255 || (fmt_yuv420(f.fmt) && mode_ != 420))) return kErrArg;
+    const size_t row = (size_t)fmt_row_bytes(f.fmt, f.width);
     const size_t stride = f.stride ? f.stride : row;
     if (stride < row) return kErrArg;
     const size_t planes = fmt_planes(f.fmt);
     const size_t plane_stride = f.plane_stride ? f.plane_stride : stride * f.height;  // (planar)
-    const size_t dev_pitch = align_up(row, 16);
-    const size_t in_bytes = (flags & kFlagDeviceInput) ? 0 : planes * dev_pitch * f.height;
+    // the device copy of a host frame: the same layout at pitch dev_pitch, plane stride
+    // dev_pitch * height (I420: a 16-byte aligned chroma pitch, half of it)
+    const bool half = fmt_yuv420(f.fmt);
+    const size_t dev_pitch = align_up(row, f.fmt == kFmtI420 ? 32 : 16);
+    const size_t dev_plane = dev_pitch * f.height;
+    const size_t crows = chroma_dim(f.height), crow = f.fmt == kFmtNv12 ? row : chroma_dim(f.width);  // (4:2:0 layouts)
+    const size_t cpitch = (size_t)fmt_chroma_pitch(f.fmt, stride), dev_cpitch = (size_t)fmt_chroma_pitch(f.fmt, dev_pitch);
+    const size_t dev_bytes = half ? dev_plane + (planes - 1) * dev_cpitch * crows : planes * dev_plane;
+    const size_t in_bytes = (flags & kFlagDeviceInput) ? 0 : dev_bytes;
     const size_t out_cap = (flags & kFlagDeviceOutput) ? 0 : max_jpeg_bytes(f.width, f.height);
     for (int i = 0; i < 64; ++i)
         if (!qy[i] || !qc[i]) return kErrArg;
@@ -795,11 +804,18 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
         s.in_plane_stride = planes > 1 ? plane_stride : 0;
     } else {
         // (planar: the planes one after the other, dev_pitch * height bytes each)
-        const size_t dev_plane = dev_pitch * f.height;
         if (stride == dev_pitch && (planes == 1 || plane_stride == dev_plane))
             // one linear copy (a 2D copy can fall back to a slower engine path)
-            JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, planes * dev_plane, hipMemcpyHostToDevice, s.stream));
-        else
+            JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, dev_bytes, hipMemcpyHostToDevice, s.stream));
+        else if (half) {
+            // the Y plane, then the chroma plane(s): NV12 one of Cb,Cr pairs, I420 Cb then Cr
+            JPGE_HIP(hipMemcpy2DAsync(s.d_in, dev_pitch, f.rgb, stride, (size_t)f.width, f.height, hipMemcpyHostToDevice,
+                                      s.stream));
+            for (size_t c = 0; c + 1 < planes; ++c)
+                JPGE_HIP(hipMemcpy2DAsync(s.d_in + dev_plane + c * dev_cpitch * crows, dev_cpitch,
+                                          f.rgb + plane_stride + c * cpitch * crows, cpitch, crow, crows,
+                                          hipMemcpyHostToDevice, s.stream));
+        } else
             for (size_t c = 0; c < planes; ++c)
                 JPGE_HIP(hipMemcpy2DAsync(s.d_in + c * dev_plane, dev_pitch, f.rgb + c * plane_stride, stride, row,
                                           f.height, hipMemcpyHostToDevice, s.stream));
@@ -1551,7 +1567,7 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     JPGE_HIP(hipSetDevice(device_));
     if (!d.rgb || !last_dc || d.width == 0 || d.height == 0 || d.width > 65535 || d.height > 65535) return kErrArg;
     if (mode_ != 420) return kErrArg;  // stripes are S420_m (the reference's subsampling)
-    if (fmt_ == kFmtRgb8Planar) return kErrArg;  // and interleaved (the stripe pointer is one row of pixels)
+    if (fmt_planes(fmt_) != 1) return kErrArg;  // and interleaved (the stripe pointer is one row of pixels)
     if (d.maxval < 1 || d.maxval > 255) return kErrRange;
     const uint32_t mh_img = (d.height + 15) / 16;
     if (d.mcu_rows == 0 || d.mcu_row0 >= mh_img || d.mcu_rows > mh_img - d.mcu_row0) return kErrArg;

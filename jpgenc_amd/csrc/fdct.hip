@@ -1,4 +1,4 @@
-// K1 fdct_kernel (gfx950): RGB8 (or another input layout, see "input layouts" below) -> YCbCr -> 4:2:0 (S420_m) -> Arai FDCT (fp64)
+// K1 fdct_kernel (gfx950): RGB8 (or another input layout, Y, Cb, Cr samples included, see "input layouts" below) -> YCbCr -> 4:2:0 (S420_m) -> Arai FDCT (fp64)
 // -> quantise -> int16 coefficients (natural order, MCU-interleaved blocks).
 //
 // One wavefront owns a tile of 4 MCUs (64x16 px) staged in LDS for the column
@@ -172,8 +172,14 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
 #define JPGE_K1_SHAPE 0
 #endif
 constexpr int kShape = JPGE_K1_SHAPE;
-static_assert(kShape >= kShapeRgb8 && kShape <= kShapePlanar, "JPGE_K1_SHAPE");
-constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kShape == kShapePlanar ? 1u : 3u;  // bytes per pixel along a row
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapeYuv444, "JPGE_K1_SHAPE");
+// The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
+// layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
+// conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
+// takes each cell's top-left word: no chroma filter.  maxval is 255 (kExact instances only).
+constexpr bool kYuv = kShape >= kShapeNv12;
+constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420;
+constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
 constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
 constexpr uint32_t kSelRgbx = 0x0C020100u, kSelBgrx = 0x0C000102u;  // perm selectors of a 4-byte pixel (0x0c: zero)
 
@@ -193,7 +199,7 @@ __device__ __forceinline__ void unpack_run(const uint4& v0, const uint4& v1, con
                                  v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
 #pragma unroll
         for (int i = 0; i < 16; ++i) px[i] = __builtin_amdgcn_perm(0u, wd[i], sel4);
-    } else if constexpr (kShape == kShapePlanar) {
+    } else if constexpr (kShape == kShapePlanar || kShape == kShapeYuv444) {
         const uint32_t r[4] = {v0.x, v0.y, v0.z, v0.w}, g[4] = {v1.x, v1.y, v1.z, v1.w}, b[4] = {v2.x, v2.y, v2.z, v2.w};
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -201,6 +207,52 @@ __device__ __forceinline__ void unpack_run(const uint4& v0, const uint4& v1, con
             const uint32_t rg = __builtin_amdgcn_perm(g[i >> 2], r[i >> 2], 0x0C0C0000u | ((4 + o8) << 8) | o8);
             px[i] = __builtin_amdgcn_perm(b[i >> 2], rg, 0x0C000100u | ((4 + o8) << 16));
         }
+    }
+}
+// The 4:2:0 layouts' run: v0 the 16 Y bytes; NV12: v1 the 8 Cb,Cr pairs of the run's cells;
+// I420: v1, v2 16 Cb and 16 Cr bytes, of which the run's cells are the low (half = 0) or
+// high 8.  Pixel i takes the chroma of cell i / 2.
+__device__ __forceinline__ void unpack_yuv420(const uint4& v0, const uint4& v1, const uint4& v2, uint32_t half,
+                                              uint32_t px[16]) {
+    const uint32_t y[4] = {v0.x, v0.y, v0.z, v0.w};
+    if constexpr (kShape == kShapeNv12) {
+        const uint32_t c[4] = {v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t o8 = (uint32_t)(i & 3), c8 = 4 + 2 * (uint32_t)((i >> 1) & 1);  // the pair's bytes of c[i / 4]
+            px[i] = __builtin_amdgcn_perm(c[i >> 2], y[i >> 2], 0x0C000000u | ((c8 + 1) << 16) | (c8 << 8) | o8);
+        }
+    } else {
+        const uint32_t cb[2] = {half ? v1.z : v1.x, half ? v1.w : v1.y}, cr[2] = {half ? v2.z : v2.x, half ? v2.w : v2.y};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t o8 = (uint32_t)(i & 3), c8 = 4 + (uint32_t)((i >> 1) & 3);
+            const uint32_t yb = __builtin_amdgcn_perm(cb[i >> 3], y[i >> 2], 0x0C0C0000u | (c8 << 8) | o8);
+            px[i] = __builtin_amdgcn_perm(cr[i >> 3], yb, 0x0C000100u | (c8 << 16));
+        }
+    }
+}
+// a staged word's samples (exact: integers)
+__device__ __forceinline__ double yuv_y(uint32_t p) { return (double)(p & 0xFF) - 128.0; }
+__device__ __forceinline__ double yuv_c(uint32_t p, int comp) { return (double)((p >> (8 * comp)) & 0xFF) - 128.0; }
+
+// One pixel of the Y, Cb, Cr shapes' clamped edge path: row sy, column sx (inside the
+// frame); a 4:2:0 layout's chroma of the pixel's cell (inside the chroma plane: the
+// clamped pixel's cell is the clamped cell).
+__device__ __forceinline__ uint32_t edge_yuv(const uint8_t* base, uint64_t stride, uint64_t plane_stride, uint32_t gh,
+                                             uint32_t sy, uint32_t sx) {
+    const uint32_t yv = base[(uint64_t)sy * stride + sx];
+    const uint8_t* c = base + plane_stride;
+    if constexpr (kShape == kShapeNv12) {
+        c += (uint64_t)(sy >> 1) * stride + 2 * (uint64_t)(sx >> 1);
+        return yv | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16);
+    } else if constexpr (kShape == kShapeI420) {
+        const uint64_t cs = (stride + 1) / 2;
+        c += (uint64_t)(sy >> 1) * cs + (sx >> 1);
+        return yv | ((uint32_t)c[0] << 8) | ((uint32_t)c[cs * ((gh + 1) / 2)] << 16);
+    } else {
+        c += (uint64_t)sy * stride + sx;
+        return yv | ((uint32_t)c[0] << 8) | ((uint32_t)c[plane_stride] << 16);
     }
 }
 
@@ -223,8 +275,8 @@ __device__ __forceinline__ uint32_t edge_pixel(const uint8_t* rgb, uint64_t stri
 // inside their row, so the range is the last row's end.
 struct RgbRsrc {
     __amdgpu_buffer_rsrc_t p0;
-#if JPGE_K1_SHAPE == 3
-    __amdgpu_buffer_rsrc_t p1, p2;
+#if JPGE_K1_SHAPE >= 3
+    __amdgpu_buffer_rsrc_t p1, p2;  // (NV12: p2 repeats p1, unused)
 #endif
 };
 __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride, uint64_t plane_stride, uint32_t gw,
@@ -233,18 +285,39 @@ __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride,
     uint8_t* b = const_cast<uint8_t*>(rgb);
     RgbRsrc r;
     r.p0 = __builtin_amdgcn_make_buffer_rsrc(b, 0, range, 0x00020000);
-#if JPGE_K1_SHAPE == 3
+#if JPGE_K1_SHAPE == 3 || JPGE_K1_SHAPE == 6
     r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, range, 0x00020000);
     r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + 2 * plane_stride, 0, range, 0x00020000);
+#elif JPGE_K1_SHAPE == 4
+    // the Cb,Cr plane: ch rows of pitch stride, 2 * cw bytes each
+    const uint32_t cw = (gw + 1) / 2, ch = (gh + 1) / 2;
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, (int)(uint32_t)(stride * (ch - 1) + 2 * (uint64_t)cw),
+                                             0x00020000);
+    r.p2 = r.p1;
+#elif JPGE_K1_SHAPE == 5
+    // the Cb plane, then the Cr plane: ch rows of pitch cs, cw bytes each
+    const uint32_t cw = (gw + 1) / 2, ch = (gh + 1) / 2;
+    const uint64_t cs = (stride + 1) / 2;
+    const int crange = (int)(uint32_t)(cs * (ch - 1) + cw);
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, crange, 0x00020000);
+    r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride + cs * ch, 0, crange, 0x00020000);
 #endif
     return r;
 }
-// the lane's run at buffer offset off (kOob: zeros)
-__device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint4& v0, uint4& v1, uint4& v2, uint4& v3) {
-#if JPGE_K1_SHAPE == 3
+// the lane's run at buffer offset off (kOob: zeros); the 4:2:0 layouts' chroma at coff
+__device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32_t coff, uint4& v0, uint4& v1, uint4& v2,
+                                         uint4& v3) {
+#if JPGE_K1_SHAPE == 3 || JPGE_K1_SHAPE == 6
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, off, 0, 0));
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, off, 0, 0));
+#elif JPGE_K1_SHAPE == 4
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff, 0, 0));
+#elif JPGE_K1_SHAPE == 5
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff, 0, 0));
+    v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, coff, 0, 0));
 #else
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
@@ -267,7 +340,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar) {
+    if constexpr (kShape == kShapePlanar || kYuv) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -284,7 +357,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     const uint32_t tiles_per_row = (mw + 3) / 4;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0;
+    // (I420: the chroma pitch, half the stride, is 16-byte aligned too)
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (kShape != kShapeI420 || (stride_ & 31) == 0);
     const int r16 = lane >> 2, c16 = lane & 3;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;     // DCT: lane -> (block of the round, column)
 
@@ -314,14 +388,28 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     // (tile numbers are wave-uniform: the tile's row and column come from scalar
     // arithmetic, and only this lane's fixed offset within the tile is per lane)
     const uint32_t lane_off = (uint32_t)r16 * (uint32_t)stride_ + (uint32_t)c16 * kRun;
+    // 4:2:0 layouts: the chroma of the run's 8 cells, in chroma row (tile row * 8 + r16 / 2) of
+    // pitch cpitch: NV12 the 16 bytes under the run, I420 the 16 bytes that hold its 8
+    uint32_t cpitch = 0, lane_coff = 0;
+    if constexpr (kYuv420) {
+        cpitch = kShape == kShapeNv12 ? (uint32_t)stride_ : (uint32_t)((stride_ + 1) / 2);
+        lane_coff = (uint32_t)(r16 >> 1) * cpitch + (kShape == kShapeNv12 ? (uint32_t)c16 : (uint32_t)(c16 >> 1)) * 16;
+    }
     auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * 4;
         const uint32_t y = mrow * 16 + r16, xs = mcol0 * 16 + c16 * 16;
-        const bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
+        bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
+        // (I420: and the 16 chroma bytes lie inside their row)
+        if constexpr (kShape == kShapeI420) ok = ok && ((xs >> 5) + 1) * 16 <= (gw_ + 1) / 2;
         const uint32_t base = (uint32_t)((uint64_t)(mrow * 16) * stride_ + (uint64_t)mcol0 * kRun);  // (uniform)
         const uint32_t off = ok ? base + lane_off : kOob;
-        load_run(rgb_rs, off, v0, v1, v2, v3);
+        uint32_t coff = kOob;
+        if constexpr (kYuv420) {
+            const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kShape == kShapeNv12 ? 16 : 8));
+            coff = ok ? cbase + lane_coff : kOob;
+        }
+        load_run(rgb_rs, off, coff, v0, v1, v2, v3);
         return ok;
     };
     // The last round's 16-byte coefficient row (kOob: none) is stored during the
@@ -379,7 +467,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     };
     auto y_inputs = [&](const uint32_t p[8], double x[8]) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = kExact ? ycc_exact_y(p[i]) : ycc_ref_y(p[i], scale);
+        for (int i = 0; i < 8; ++i) x[i] = kYuv ? yuv_y(p[i]) : kExact ? ycc_exact_y(p[i]) : ycc_ref_y(p[i], scale);
     };
     auto c_inputs = [&](const uint2 c[16], double x[8]) {
         if constexpr (kExact) {
@@ -406,8 +494,15 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
                     sb += (t0.y >> 16) + (t1.y >> 16);
                 }
                 const double dr = (double)sr, dg = (double)sg, db = (double)sb;
-                vb[i] = __builtin_fma(kCbB * f, db, __builtin_fma(kCbG * f, dg, (kCbR * f) * dr));
-                vr[i] = __builtin_fma(kCrB * f, db, __builtin_fma(kCrG * f, dg, (kCrR * f) * dr));
+                if constexpr (kYuv) {
+                    // Y, Cb, Cr words: the sums are of Cb (bits 8-15) and Cr (16-23) samples, and
+                    // the filter of the samples v - 128 is f * sum - 128, exact (sums below 2^10)
+                    vb[i] = dg * f - 128.0;
+                    vr[i] = db * f - 128.0;
+                } else {
+                    vb[i] = __builtin_fma(kCbB * f, db, __builtin_fma(kCbG * f, dg, (kCbR * f) * dr));
+                    vr[i] = __builtin_fma(kCrB * f, db, __builtin_fma(kCrG * f, dg, (kCrR * f) * dr));
+                }
             }
             // lanes < 32 (Cb) keep Cb of samples 0-3 and receive Cb of 4-7; lanes >= 32 (Cr)
             // receive Cr of 0-3 and keep Cr of 4-7
@@ -459,7 +554,9 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         // (the prefetched registers are consumed on every path, so no later wait on
         // them can also drain the previous tile's coefficient stores)
         uint32_t px[16];
-        if constexpr (kShape == kShapeX4 || kShape == kShapePlanar) {
+        if constexpr (kYuv420) {
+            unpack_yuv420(c0, c1, c2, (uint32_t)(c16 & 1), px);
+        } else if constexpr (kShape == kShapeX4 || kShape == kShapePlanar || kShape == kShapeYuv444) {
             unpack_run(c0, c1, c2, c3, sel4_, px);
         } else {
             const uint4 v0 = c0, v1 = c1, v2 = c2;
@@ -474,7 +571,10 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         }
         if (!cfast) {  // right/bottom edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
+            if constexpr (kYuv)
+                for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sy, min(xs + i, gw_ - 1));
+            else
+                for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
         uint32_t* dst = &W.rgbx[r16 * kRgbPitch + c16 * 16];
 #pragma unroll
@@ -576,7 +676,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar) {
+    if constexpr (kShape == kShapePlanar || kYuv) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -596,7 +696,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     const uint32_t tiles_per_row = (mw + kMcus - 1) / kMcus;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0;
+    // (I420: the chroma pitch, half the stride, is 16-byte aligned too)
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (kShape != kShapeI420 || (stride_ & 31) == 0);
     const int r8 = lane >> 3, c8 = lane & 7;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;   // DCT: lane -> (block of the round, column)
 
@@ -620,7 +721,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         const bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
         const uint32_t base = (uint32_t)((uint64_t)(mrow * 8) * stride_ + (uint64_t)mcol0 * (kRun / 2) * kYh);  // (uniform)
         const uint32_t off = ok ? base + lane_off : kOob;
-        load_run(rgb_rs, off, v0, v1, v2, v3);
+        load_run(rgb_rs, off, kOob, v0, v1, v2, v3);
         return ok;
     };
     u32x4 pend;
@@ -668,7 +769,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
 
         uint32_t px[16];
-        if constexpr (kShape == kShapeX4 || kShape == kShapePlanar) {
+        if constexpr (kShape == kShapeX4 || kShape == kShapePlanar || kShape == kShapeYuv444) {
             unpack_run(c0, c1, c2, c3, sel4_, px);
         } else {
             const uint4 v0 = c0, v1 = c1, v2 = c2;
@@ -683,7 +784,10 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         }
         if (!cfast) {  // edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
+            if constexpr (kYuv)
+                for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sy, min(xs + i, gw_ - 1));
+            else
+                for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
         uint32_t* dst = &W.rgbx[r8 * kRgbPitch444 + c8 * 16];
 #pragma unroll
@@ -714,7 +818,10 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
             double x[8];
             if (comp == 0) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) x[i] = kExact ? ycc_exact_y(p[i]) : ycc_ref_y(p[i], scale);
+                for (int i = 0; i < 8; ++i) x[i] = kYuv ? yuv_y(p[i]) : kExact ? ycc_exact_y(p[i]) : ycc_ref_y(p[i], scale);
+            } else if constexpr (kYuv) {  // the kept sample itself
+#pragma unroll
+                for (int i = 0; i < 8; ++i) x[i] = yuv_c(p[i], comp);
             } else {
                 const double kr = comp == 2 ? kCrR : kCbR, kg = comp == 2 ? kCrG : kCbG, kb = comp == 2 ? kCrB : kCbB;
 #pragma unroll
@@ -781,9 +888,11 @@ static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, h
     const bool ex = a.maxval == 255;
     if (k1_whole_cu(a.g, a.solo)) {
         if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
     } else {
         if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     }
 }
@@ -794,9 +903,11 @@ static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hi
     const bool ex = a.maxval == 255;
     if (k1_whole_cu(a.g, a.solo)) {
         if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
     } else {
         if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     }
 }
@@ -806,26 +917,33 @@ template <int kN>
 static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     const FdctArgs& a = fs.a[0];
     // the kernels assume these shapes (kernels.hpp Geometry)
-    if (a.g.row8()) {
-        switch (a.g.yh) {
-            // (launch_timed returns the launch's error: hipGetLastError has already consumed it)
-            case 1: return a.g.bpm != 3 ? hipErrorInvalidValue : launch_row8<1, kN>(fs, grid, s, t);
-            case 2: return a.g.bpm != 4 ? hipErrorInvalidValue : launch_row8<2, kN>(fs, grid, s, t);
-            case 4: return a.g.bpm != 6 ? hipErrorInvalidValue : launch_row8<4, kN>(fs, grid, s, t);
+    if constexpr (kYuv420) {
+        // the chroma planes are the S420_m planes already: the instance that takes each 2x2
+        // cell's first staged word (all four hold the cell's sample) applies no filter
+        if (a.g.row8() || a.g.yh != 2 || a.g.bpm != 6 || a.g.cfilt != kFiltS420m) return hipErrorInvalidValue;
+        return launch_420<kFiltS420, kN>(fs, grid, s, t);
+    } else {
+        if (a.g.row8()) {
+            switch (a.g.yh) {
+                // (launch_timed returns the launch's error: hipGetLastError has already consumed it)
+                case 1: return a.g.bpm != 3 ? hipErrorInvalidValue : launch_row8<1, kN>(fs, grid, s, t);
+                case 2: return a.g.bpm != 4 ? hipErrorInvalidValue : launch_row8<2, kN>(fs, grid, s, t);
+                case 4: return a.g.bpm != 6 ? hipErrorInvalidValue : launch_row8<4, kN>(fs, grid, s, t);
+                default: return hipErrorInvalidValue;
+            }
+        }
+        if (a.g.yh != 2 || a.g.bpm != 6) return hipErrorInvalidValue;
+        switch (a.g.cfilt) {
+            case kFiltS420m: return launch_420<kFiltS420m, kN>(fs, grid, s, t);
+            case kFiltS420lm: return launch_420<kFiltS420lm, kN>(fs, grid, s, t);
+            case kFiltS420: return launch_420<kFiltS420, kN>(fs, grid, s, t);
             default: return hipErrorInvalidValue;
         }
-    }
-    if (a.g.yh != 2 || a.g.bpm != 6) return hipErrorInvalidValue;
-    switch (a.g.cfilt) {
-        case kFiltS420m: return launch_420<kFiltS420m, kN>(fs, grid, s, t);
-        case kFiltS420lm: return launch_420<kFiltS420lm, kN>(fs, grid, s, t);
-        case kFiltS420: return launch_420<kFiltS420, kN>(fs, grid, s, t);
-        default: return hipErrorInvalidValue;
     }
 }
 
 #if JPGE_K1_SHAPE != 0
-// this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar)
+// this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
@@ -833,6 +951,9 @@ hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, h
 hipError_t launch_fdct_bgr8(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_x4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_planar(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_nv12(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_i420(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_yuv444(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 
 uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs) {
     const uint32_t tiles = k1_tiles(g);
@@ -856,8 +977,9 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         // 32-bit buffer offsets: the frame's pixels and coefficients must stay below kOob
         // (a 16384^2 frame needs 805 MB of each)
         // (planar: each plane has its own descriptor, so the extent is one plane's)
-        if (m.fmt < 0 || m.fmt >= kFmtCount || m.g.height == 0) return hipErrorInvalidValue;
-        const uint64_t row = (uint64_t)fmt_bpp(m.fmt) * m.g.width;
+        // (the 4:2:0 layouts' chroma planes have descriptors of their own, with smaller extents)
+        if (!fmt_valid(m.fmt) || m.g.height == 0 || (fmt_yuv(m.fmt) && m.maxval != 255)) return hipErrorInvalidValue;
+        const uint64_t row = fmt_row_bytes(m.fmt, m.g.width);
         const uint64_t extent = m.stride * (m.g.height - 1) + row;  // the descriptor's range
         if (m.stride < row || extent >= kOob || (uint64_t)m.stride * m.g.height >= kOob ||
             (uint64_t)m.g.nblocks() * 128 >= kOob)
@@ -877,6 +999,9 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
     switch (fmt_shape(a.fmt)) {
         case kShapeBgr8: return launch_fdct_bgr8(w, grid, s, t);
         case kShapeX4: return launch_fdct_x4(w, grid, s, t);
+        case kShapeNv12: return launch_fdct_nv12(w, grid, s, t);
+        case kShapeI420: return launch_fdct_i420(w, grid, s, t);
+        case kShapeYuv444: return launch_fdct_yuv444(w, grid, s, t);
         default: return launch_fdct_planar(w, grid, s, t);
     }
 }

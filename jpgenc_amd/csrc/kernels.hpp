@@ -50,16 +50,37 @@ JPGE_HD inline int block_comp(int k, uint32_t bpm) { return k < (int)bpm - 2 ? 0
 // Input layouts (jpge.h JPGE_FMT_*, the same values) and K1's load shapes: what a lane
 // loads for its 16-pixel run.  Each shape is one build of fdct.hip (JPGE_K1_SHAPE).
 constexpr int kFmtRgb8 = 0, kFmtBgr8 = 1, kFmtRgba8 = 2, kFmtBgra8 = 3, kFmtRgb8Planar = 4, kFmtCount = 5;
+// full-range 8-bit Y, Cb, Cr samples (no colour conversion; a sample v is the fp64 value v - 128):
+// NV12 (Y plane + one plane of interleaved Cb,Cr at half size), I420 (Y, Cb, Cr planes,
+// chroma at half size), planar 4:4:4 (addressed as kFmtRgb8Planar)
+constexpr int kFmtNv12 = 16, kFmtI420 = 17, kFmtYuv444Planar = 18;
+JPGE_HD inline bool fmt_valid(int fmt) { return (fmt >= 0 && fmt < kFmtCount) || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar); }
+JPGE_HD inline bool fmt_yuv(int fmt) { return fmt >= kFmtNv12; }
+JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420; }  // chroma planes at half size
 constexpr int kShapeRgb8 = 0;    // 48 bytes R,G,B,...: three b128 loads
 constexpr int kShapeBgr8 = 1;    // the same loads, bytes 2,1,0 of each pixel
 constexpr int kShapeX4 = 2;      // RGBA8 / BGRA8: 64 bytes, four b128 loads, a wave-uniform byte selector
 constexpr int kShapePlanar = 3;  // 16 bytes of each of the planes R, G, B: three b128 loads
+constexpr int kShapeNv12 = 4;    // 16 Y bytes + the 16 Cb,Cr bytes (8 samples of both) under them: two b128 loads
+constexpr int kShapeI420 = 5;    // 16 Y bytes + 16 Cb bytes + 16 Cr bytes (the lane uses 8 of each): three b128 loads
+constexpr int kShapeYuv444 = 6;  // the planar shape's loads of the planes Y, Cb, Cr
 JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar : kShapeX4;
+    return fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
+         : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
 }
 // bytes per pixel within a row (planar: of one plane), and planes
-JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtRgb8Planar ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
-JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt == kFmtRgb8Planar ? 3u : 1u; }
+JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
+JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt == kFmtNv12 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
+// The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
+// that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs).
+JPGE_HD inline uint64_t fmt_row_bytes(int fmt, uint32_t width) {
+    return fmt == kFmtNv12 ? ((uint64_t)width + 1) & ~(uint64_t)1 : (uint64_t)fmt_bpp(fmt) * width;
+}
+// The 4:2:0 layouts' chroma: ceil(height / 2) rows of ceil(width / 2) samples, starting
+// plane_stride bytes after the Y plane; row pitch `stride` (NV12, 2 bytes per sample) or
+// (stride + 1) / 2 (I420, whose Cr plane follows the Cb plane's rows).
+JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) { return fmt == kFmtI420 ? (stride + 1) / 2 : stride; }
+JPGE_HD inline uint32_t chroma_dim(uint32_t n) { return (n + 1) / 2; }
 
 constexpr int kHistReplicas = 8;  // spread of the global histogram atomics
 constexpr int kStatsTile = 128;           // blocks per statistics tile (4 lanes each)
@@ -95,6 +116,7 @@ struct FdctArgs {
     uint32_t imp_n16;
     uint64_t* dbg;   // diagnostic phase stamps (JPGE_STAMPS builds), else unused
     // input layout (kFmt*); planar: plane c's rows start at rgb + c * plane_stride
+    // (NV12, I420: the chroma starts at rgb + plane_stride, see fmt_chroma_pitch)
     int fmt = kFmtRgb8;
     uint64_t plane_stride = 0;
 };

@@ -155,6 +155,18 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
 #define JPGE_FMT_NV12 16
 #define JPGE_FMT_I420 17
 #define JPGE_FMT_YUV444_PLANAR 18
+/* One plane of 8-bit luminance: `height` rows of `stride` bytes (0 = width), one byte per
+ * pixel; a sample v enters the transform as the value v - 128, as a Y sample above.
+ * maxval must be 255 and plane_stride 0 (else JPGE_E_ARG).  The output is a baseline JPEG
+ * with ONE component in a non-interleaved scan (ITU T.81 A.2.2): SOI APP0 DQT(qy) SOF0
+ * (1 component, 1x1, table 0) DHT(DC 0) DHT(AC 0) [DRI] SOS <entropy> EOI.  The MCU is
+ * one 8x8 block: the plane is edge-replicated to whole blocks, blocks and the DC chain run
+ * in block raster order, and a restart interval counts blocks.  qc is not read (it may be
+ * NULL in the encode and stage entries) and the context's subsampling mode does not enter:
+ * there is no chroma.  jpge_fdct_quant fills coef_y only (coef_cb, coef_cr may be NULL);
+ * jpge_symbol_stats returns zeros and ~0 keys for tables 2 and 3.  The fast path needs the
+ * pointer and the stride 16-byte aligned. */
+#define JPGE_FMT_GRAY8 8
 
 /* Input layout for the context's following jpge_encode_rgb8, jpge_encode_batch,
  * jpge_fdct_quant and jpge_symbol_stats calls (their `rgb` then points at a frame in
@@ -168,7 +180,8 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
  * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
  * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
- * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
+ * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR) and for JPGE_FMT_GRAY8 (stripes
+ * are three-component 4:2:0); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
 int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
 /* the current setting (plane_stride may be NULL) */
 int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride);
@@ -261,12 +274,15 @@ typedef struct {
     uint8_t qy[64], qc[64];  /* DQT tables, natural order */
 } jpge_decoded;
 
-/* Baseline entropy decode of a .jpg written by this library (SOF0, three
- * components, chroma 1x1, Y 1x1 / 2x1 / 4x1 / 2x2, optional DRI/RSTn): the
+/* Baseline entropy decode of a .jpg written by this library (SOF0; three
+ * components, chroma 1x1, Y 1x1 / 2x1 / 4x1 / 2x2, or one component 1x1, the
+ * JPGE_FMT_GRAY8 stream; optional DRI/RSTn): the
  * quantised coefficients with the DC differences undone (Image.cpp:638-678
  * inverted), natural order, blocks in raster order per component — the planes
- * jpge_fdct_quant returns.  y = NULL: fill *info only (sizes).  Verification
- * utility, not on the encode path. */
+ * jpge_fdct_quant returns.  y = NULL: fill *info only (sizes).  A one-component
+ * stream reports yh = yv = 1, c_blocks = 0 (how a caller tells it) and a zero qc;
+ * cb and cr may then be NULL and are not written.  Verification utility, not on
+ * the encode path. */
 int jpge_decode_coeffs(const uint8_t* jpg, size_t len, jpge_decoded* info, int16_t* y, int16_t* cb, int16_t* cr,
                        size_t cap_y_blocks, size_t cap_c_blocks);
 

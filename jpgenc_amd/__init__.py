@@ -30,6 +30,9 @@ JPGE_FMT_RGB8, JPGE_FMT_BGR8, JPGE_FMT_RGBA8, JPGE_FMT_BGRA8, JPGE_FMT_RGB8_PLAN
 #: host frames from pack_yuv420), and planar (3, H, W)
 JPGE_FMT_NV12, JPGE_FMT_I420, JPGE_FMT_YUV444_PLANAR = 16, 17, 18
 _FMT_420 = (JPGE_FMT_NV12, JPGE_FMT_I420)
+#: one (H, W) plane of 8-bit luminance -> a one-component (grayscale) JPEG; no chroma: the
+#: chroma table and the subsampling mode do not enter
+JPGE_FMT_GRAY8 = 8
 
 #: subsampling modes (jpge.h JPGE_S*) -> (Y blocks across, Y blocks down) an MCU
 SUBSAMPLING = {420: (2, 2), 4200: (2, 2), 4201: (2, 2), 444: (1, 1), 422: (2, 1), 411: (4, 1)}
@@ -286,11 +289,16 @@ def idct8x8(block) -> np.ndarray:
 
 def decode_coeffs(data: bytes):
     """Entropy-decode a jpge .jpg -> (Decoded header, Y, Cb, Cr) quantised coefficient
-    planes of shape (blocks, 64), raster block order, natural order (jpge_decode_coeffs)."""
+    planes of shape (blocks, 64), raster block order, natural order (jpge_decode_coeffs).
+    A one-component (grayscale) file gives (header, Y, None, None); its c_blocks is 0."""
     buf = np.frombuffer(bytes(data), np.uint8)
     info = Decoded()
     _check(lib().jpge_decode_coeffs(_p(buf), buf.size, ctypes.byref(info), None, None, None, 0, 0), "decode_coeffs")
     y = np.zeros((info.y_blocks, 64), np.int16)
+    if info.c_blocks == 0:
+        _check(lib().jpge_decode_coeffs(_p(buf), buf.size, ctypes.byref(info), _p(y), None, None, y.shape[0], 0),
+               "decode_coeffs")
+        return info, y, None, None
     cb = np.zeros((info.c_blocks, 64), np.int16)
     cr = np.zeros_like(cb)
     _check(lib().jpge_decode_coeffs(_p(buf), buf.size, ctypes.byref(info), _p(y), _p(cb), _p(cr), y.shape[0],
@@ -455,8 +463,14 @@ def pack_yuv420(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
 
 def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     """(width, height, row stride in bytes) of a C-contiguous frame shaped for layout `fmt`:
-    (H, W, 3), (H, W, 4) or (3, H, W); NV12 and I420: a pack_yuv420 frame of that layout."""
+    (H, W, 3), (H, W, 4) or (3, H, W); GRAY8: (H, W); NV12 and I420: a pack_yuv420 frame of
+    that layout."""
     bpp, planes = input_format_info(fmt)
+    if fmt == JPGE_FMT_GRAY8:
+        if a.ndim != 2 or a.dtype != np.uint8 or a.size == 0:
+            raise ValueError(f"frame of shape {a.shape} and type {a.dtype}: input layout {fmt} (GRAY8) takes "
+                             "a non-empty (H, W) uint8 array")
+        return a.shape[1], a.shape[0], a.shape[1]
     if fmt in _FMT_420:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
                 a.size != yuv420_bytes(fmt, a.width, a.height, a.stride):
@@ -471,7 +485,9 @@ def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
 
 def _as_frame(a, fmt: int):
     """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
-    if fmt not in _FMT_420:
+    if fmt == JPGE_FMT_GRAY8:
+        a = np.ascontiguousarray(a)  # (the type is checked, not converted: a float plane is no gray frame)
+    elif fmt not in _FMT_420:
         a = np.ascontiguousarray(a, np.uint8)
     w, h, stride = _frame_geom(a, fmt)
     return np.ascontiguousarray(a, np.uint8), w, h, stride
@@ -570,7 +586,8 @@ class Encoder:
 
     def set_input_format(self, fmt: int, plane_stride: int = 0) -> None:
         """Input layout of the following encodes (JPGE_FMT_*): frames are then (H, W, 3),
-        (H, W, 4) or, planar, (3, H, W); NV12 and I420: pack_yuv420 frames.  plane_stride:
+        (H, W, 4) or, planar, (3, H, W); GRAY8: (H, W), written as a one-component JPEG;
+        NV12 and I420: pack_yuv420 frames.  plane_stride:
         bytes between the planes of the raw-pointer entries' planar frames (NV12, I420: from
         the Y plane to the chroma; 0 = stride * height)."""
         _check(lib().jpge_set_input_format(self._ctx, int(fmt), int(plane_stride)), "set_input_format")
@@ -587,6 +604,10 @@ class Encoder:
         _check(lib().jpge_get_lanes(self._ctx, ctypes.byref(n)), "get_lanes")
         return n.value
 
+    def _gray_qc(self, qy, qc):
+        # (GRAY8 reads no chroma table: a caller's luma table alone is a whole setting)
+        return qy if qc is None and self._fmt == JPGE_FMT_GRAY8 else qc
+
     @staticmethod
     def _tables(quality, qy, qc):
         if qy is None or qc is None:
@@ -597,7 +618,7 @@ class Encoder:
         """Image::writeJPEG (Image.cpp:831-976) on an (H, W, 3) uint8 frame -> .jpg bytes
         (the frame shaped for the input layout, set_input_format)."""
         rgb, w, h, stride = _as_frame(rgb, self._fmt)
-        qy, qc = self._tables(quality, qy, qc)
+        qy, qc = self._tables(quality, qy, self._gray_qc(qy, qc))
         out = np.empty(max_jpeg_bytes(w, h), np.uint8)
         n = ctypes.c_size_t()
         _check(lib().jpge_encode_rgb8(self._ctx, _p(rgb), w, h, stride, int(maxval), _p(qy), _p(qc), _p(out),
@@ -620,7 +641,8 @@ class Encoder:
     def encode_tensor(self, t, quality: int = 50, out=None, order: str = "rgb", maxval: int = 255, layout=None):
         """One torch uint8 tensor through jpge_encode_rgb8 without a repack: (3, H, W) is the
         planar layout (plane stride t.stride(0)), (H, W, 3) and (H, W, 4) the interleaved ones
-        in channel order `order` ("rgb" or "bgr"; planar tensors are R, G, B).  Any row stride;
+        in channel order `order` ("rgb" or "bgr"; planar tensors are R, G, B); a 2-dimensional
+        (H, W) tensor is a gray plane (JPGE_FMT_GRAY8: a one-component JPEG).  Any row stride;
         the inner dimension must have unit stride (else ValueError).  A device tensor is read
         in place (JPGE_DEVICE_INPUT), a host tensor goes the host path.  Returns the .jpg
         bytes, or, with `out` a uint8 tensor on the frame's device, writes them there and
@@ -631,16 +653,25 @@ class Encoder:
             raise ValueError(f"layout {layout!r}: 'chw' or 'hwc'")
         if order not in ("rgb", "bgr"):
             raise ValueError(f"order {order!r}: 'rgb' or 'bgr'")
-        if t.dim() != 3 or t.element_size() != 1 or t.dtype.is_floating_point:
-            raise ValueError("encode_tensor takes a 3-dimensional uint8 tensor")
+        if t.dim() not in (2, 3) or t.element_size() != 1 or t.dtype.is_floating_point:
+            raise ValueError("encode_tensor takes a 3-dimensional (colour) or 2-dimensional (gray) uint8 tensor")
         shape, st = tuple(t.shape), tuple(t.stride())
         plane_stride = 0
-        hwc, chw = shape[2] in (3, 4), shape[0] == 3
+        gray = t.dim() == 2
+        hwc, chw = not gray and shape[2] in (3, 4), not gray and shape[0] == 3
         if hwc and chw and layout is None:
             raise ValueError(f"tensor of shape {shape} is (3, H, W) or (H, W, C): pass layout='chw' or 'hwc'")
         if layout is not None:
             hwc, chw = hwc and layout == "hwc", chw and layout == "chw"
-        if hwc:  # (H, W, C)
+        if gray:  # (H, W)
+            if shape[0] == 0 or shape[1] == 0:
+                raise ValueError(f"tensor of shape {shape}: an empty frame")
+            if st[1] != 1 and shape[1] > 1:
+                raise ValueError(f"strides {st}: the inner dimension must have unit stride")
+            h, w, stride, fmt = shape[0], shape[1], st[0], JPGE_FMT_GRAY8
+            if h == 1:
+                stride = w  # (one row: any pitch)
+        elif hwc:  # (H, W, C)
             if st[2] != 1 or (st[1] != shape[2] and shape[1] > 1):  # (one pixel per row: any pixel stride)
                 raise ValueError(f"strides {st}: the inner dimension must have unit stride (pixels packed)")
             h, w, stride = shape[0], shape[1], st[0]
@@ -653,7 +684,7 @@ class Encoder:
                 raise ValueError(f"strides {st}: the inner dimension must have unit stride")
             h, w, stride, plane_stride, fmt = shape[1], shape[2], st[1], st[0], JPGE_FMT_RGB8_PLANAR
         else:
-            raise ValueError(f"tensor of shape {shape}: (3, H, W), (H, W, 3) or (H, W, 4)")
+            raise ValueError(f"tensor of shape {shape}: (3, H, W), (H, W, 3), (H, W, 4) or (H, W)")
         if stride < w * input_format_info(fmt)[0] and h > 1:
             raise ValueError("rows overlap")
         flags = JPGE_DEVICE_INPUT if t.is_cuda else 0
@@ -794,8 +825,15 @@ class Encoder:
 
     def fdct_quant(self, rgb: np.ndarray, quality: int = 50, maxval: int = 255, qy=None, qc=None):
         """Stage dump: quantised coefficients (before DC diff) -> (Y, Cb, Cr) arrays of shape
-        (nblocks, 64), blocks in raster order, natural order within a block."""
+        (nblocks, 64), blocks in raster order, natural order within a block.  GRAY8: (Y, None,
+        None), the ceil(W/8) * ceil(H/8) blocks of the one component."""
         rgb, w, h, stride = _as_frame(rgb, self._fmt)
+        if self._fmt == JPGE_FMT_GRAY8:
+            y = np.zeros((-(-w // 8) * -(-h // 8), 64), np.int16)
+            qy, qc = self._tables(quality, qy, self._gray_qc(qy, qc))
+            _check(lib().jpge_fdct_quant(self._ctx, _p(rgb), w, h, stride, int(maxval), _p(qy), None, _p(y), None,
+                                         None, 0), "fdct_quant")
+            return y, None, None
         yh, yv = SUBSAMPLING[getattr(self, "_sub", 420)]
         mw, mh = -(-w // (8 * yh)), -(-h // (8 * yv))  # MCUs across / down
         y = np.zeros((mw * yh * mh * yv, 64), np.int16)

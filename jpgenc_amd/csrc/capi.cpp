@@ -299,9 +299,10 @@ static int encode_pixels(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t
                          const uint8_t qy[64], const uint8_t qc[64], uint8_t* out, size_t cap, size_t* len,
                          uint32_t flags, bool use_format) {
     CtxUse use(ctx);
-    if (!use || !rgb || !qy || !qc || !out || !len) return JPGE_E_ARG;
+    if (!use || !rgb || !qy || !out || !len) return JPGE_E_ARG;
     jpge::FrameDesc f = frame(rgb, w, h, stride, maxval);
     if (use_format) ctx->enc->apply_input_format(f);
+    if (!qc && !jpge::fmt_gray(f.fmt)) return JPGE_E_ARG;  // (one component: qc is not read)
     f.out = out;
     f.cap = cap;
     int st = ctx->enc->encode(f, qy, qc, flags);
@@ -318,14 +319,17 @@ int jpge_encode_rgb8(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, 
 int jpge_encode_batch(jpge_ctx* ctx, jpge_frame* frames, int n, const uint8_t qy[64], const uint8_t qc[64],
                       uint32_t flags) {
     CtxUse use(ctx);
-    if (!use || (!frames && n) || n < 0 || !qy || !qc) return JPGE_E_ARG;
+    if (!use || (!frames && n) || n < 0 || !qy) return JPGE_E_ARG;
     std::vector<jpge::FrameDesc> fd(n);
+    bool need_qc = n == 0;  // (one component: qc is not read)
     for (int i = 0; i < n; ++i) {
         fd[i] = frame(frames[i].rgb, frames[i].width, frames[i].height, frames[i].stride, frames[i].maxval);
         ctx->enc->apply_input_format(fd[i]);
+        need_qc = need_qc || !jpge::fmt_gray(fd[i].fmt);
         fd[i].out = frames[i].out;
         fd[i].cap = frames[i].cap;
     }
+    if (!qc && need_qc) return JPGE_E_ARG;
     int st = ctx->enc->encode_batch(fd.data(), n, qy, qc, flags);
     for (int i = 0; i < n; ++i) {
         frames[i].len = fd[i].len;
@@ -338,9 +342,11 @@ int jpge_fdct_quant(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, s
                     const uint8_t qy[64], const uint8_t qc[64], int16_t* cy, int16_t* ccb, int16_t* ccr,
                     uint32_t flags) {
     CtxUse use(ctx);
-    if (!use || !rgb || !qy || !qc || !cy || !ccb || !ccr) return JPGE_E_ARG;
+    if (!use || !rgb || !qy || !cy) return JPGE_E_ARG;
     jpge::FrameDesc f = frame(rgb, w, h, stride, maxval);
     ctx->enc->apply_input_format(f);
+    // (one component: qc is not read, and coef_cb / coef_cr are not written)
+    if (!jpge::fmt_gray(f.fmt) && (!qc || !ccb || !ccr)) return JPGE_E_ARG;
     return ctx->enc->fdct_quant(f, qy, qc, flags, cy, ccb, ccr);
 }
 
@@ -348,9 +354,10 @@ int jpge_symbol_stats(jpge_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h,
                       const uint8_t qy[64], const uint8_t qc[64], uint32_t counts[1024], uint64_t first[1024],
                       uint32_t flags) {
     CtxUse use(ctx);
-    if (!use || !rgb || !qy || !qc || !counts || !first) return JPGE_E_ARG;
+    if (!use || !rgb || !qy || !counts || !first) return JPGE_E_ARG;
     jpge::FrameDesc f = frame(rgb, w, h, stride, maxval);
     ctx->enc->apply_input_format(f);
+    if (!qc && !jpge::fmt_gray(f.fmt)) return JPGE_E_ARG;  // (one component: qc is not read)
     return ctx->enc->symbol_stats(f, qy, qc, flags, counts, first);
 }
 

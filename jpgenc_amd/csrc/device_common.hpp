@@ -108,8 +108,10 @@ constexpr int kPartsPerBlock = 4;  // lanes cooperating on one block's non-zero 
 // The predecessor is at most 6 blocks back (bpm <= 6).  In every mode the Y chain
 // runs in MCU order over the MCU's bpm - 2 Y slots, so an MCU's first Y block
 // follows the previous MCU's last (3 blocks back: past Cr and Cb), and each chroma
-// block follows the same slot of the previous MCU.
+// block follows the same slot of the previous MCU.  One component (bpm = 1): the
+// chain is the block order itself, block g follows block g - 1.
 __device__ __forceinline__ int64_t dc_pred_index(uint64_t g, uint32_t bpm) {
+    if (bpm == 1) return (int64_t)g - 1;  // (-1 for the first block)
     const int k = (int)(g % bpm);
     if (k >= 1 && k < (int)bpm - 2) return (int64_t)g - 1;
     if (g < bpm) return -1;

@@ -54,6 +54,18 @@ inline Geometry geometry(uint32_t w, uint32_t h, int mode = 420) {
     return g;
 }
 
+// One component (kFmtGray8): the frame in single 8x8 blocks, no chroma (kernels.hpp Geometry)
+inline Geometry gray_geometry(uint32_t w, uint32_t h) {
+    Geometry g;
+    g.width = w;
+    g.height = h;
+    g.yh = 1;
+    g.bpm = 1;
+    g.mw = (w + 7) / 8;
+    g.mh = (h + 7) / 8;
+    return g;
+}
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Host-side wait with low wake-up latency (the pipeline waits on short intervals).
@@ -771,10 +783,14 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
                    Slot* imp, FdctArgs& a, StatsArgs& st) {
     if (!f.rgb || f.width == 0 || f.height == 0 || f.width > 65535 || f.height > 65535) return kErrArg;
     if (f.maxval < 1 || f.maxval > 255) return kErrRange;
-    const Geometry g = geometry(f.width, f.height, mode_);
+    // (one component: no chroma, so the subsampling mode does not enter, and qc is not read)
+    const bool gray = fmt_gray(f.fmt);
+    const Geometry g = gray ? gray_geometry(f.width, f.height) : geometry(f.width, f.height, mode_);
     if (!fmt_valid(f.fmt) || (f.plane_stride && fmt_planes(f.fmt) == 1)) return kErrArg;
     // Y, Cb, Cr samples are 8-bit, and half-size chroma planes are the S420_m mode's planes
     if (fmt_yuv(f.fmt) && (f.maxval != 255 || (fmt_yuv420(f.fmt) && mode_ != 420))) return kErrArg;
+    if (gray && f.maxval != 255) return kErrArg;
+    if (gray) qc = qy;
     const size_t row = (size_t)fmt_row_bytes(f.fmt, f.width);
     const size_t stride = f.stride ? f.stride : row;
     if (stride < row) return kErrArg;
@@ -953,14 +969,21 @@ int Encoder::build_tables_from(Slot& s, const uint32_t* cnt_all, const uint64_t*
         ok[t] = inverted ? build_table_inverted(cnt_all + t * 256, first_all + t * 256, tabs[t])
                          : build_table(cnt_all + t * 256, first_all + t * 256, tabs[t]);
     };
-    if (helper && helper->post(cnt_all, first_all, inverted, tabs, ok)) {
+    const bool gray = s.g.gray();
+    if (gray) {
+        // one component: the two luma tables; the chroma texts are empty and never reach the
+        // builder, and their slots of the table block stay unused (zeroed)
+        parallel_for(2, parallel ? 2 : 1, one);
+        ok[2] = ok[3] = 1;
+        std::memset(s.h_tab + 2 * 256, 0, 2 * 256 * sizeof(uint32_t));
+    } else if (helper && helper->post(cnt_all, first_all, inverted, tabs, ok)) {
         one(1);  // (the luma AC table here, the other three on the helper)
         helper->wait();
     } else {
         parallel_for(4, parallel ? 4 : 1, one);
     }
     const int64_t t1 = cpu_prof_ ? thread_ns() : 0;
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < (gray ? 2 : 4); ++t)
         if (ok[t])
             for (int i = 0; i < 256; ++i)
                 s.h_tab[t * 256 + i] = ((uint32_t)tabs[t].len[i] << 16) | (tabs[t].code[i] & 0xFFFF);
@@ -982,8 +1005,9 @@ int Encoder::build_tables_from(Slot& s, const uint32_t* cnt_all, const uint64_t*
         return kErrInternal;
     }
     const HuffTable* tp[4] = {&tabs[0], &tabs[1], &tabs[2], &tabs[3]};
-    const std::vector<uint8_t> hdr = jfif_headers(s.img_w, s.img_h, s.qy, s.qc, tp, restart_mcus_,
-                                                    (uint8_t)((s.g.yh << 4) | s.g.yv()));
+    const std::vector<uint8_t> hdr = gray ? jfif_headers_gray(s.img_w, s.img_h, s.qy, tp, restart_mcus_)
+                                          : jfif_headers(s.img_w, s.img_h, s.qy, s.qc, tp, restart_mcus_,
+                                                         (uint8_t)((s.g.yh << 4) | s.g.yv()));
     if (hdr.size() > kHdrMax) return kErrInternal;
     std::memcpy(reinterpret_cast<uint8_t*>(s.h_tab) + kTabBytes, hdr.data(), hdr.size());
     s.hdr_len = hdr.size();
@@ -1253,8 +1277,8 @@ int Encoder::batch_set_size(const FrameDesc* fr, int n) const {
             fr[i].fmt != f0.fmt)
             return 1;
     const bool placed_in_code = (ext_place_ > 0 || (ext_place_ < 0 && lanes_.size() > 1)) && place_in_code_;
-    if (!placed_in_code || restart_mcus_ || layout(geometry(f0.width, f0.height, mode_)).grid() > kPlaceInCodeMaxWgs)
-        return 1;
+    const Geometry g0 = fmt_gray(f0.fmt) ? gray_geometry(f0.width, f0.height) : geometry(f0.width, f0.height, mode_);
+    if (!placed_in_code || restart_mcus_ || layout(g0).grid() > kPlaceInCodeMaxWgs) return 1;
     if (set_) return set_;
     const uint64_t k = kSetPixels / ((uint64_t)f0.width * f0.height);
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(kMaxSet, k));
@@ -1567,7 +1591,7 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     JPGE_HIP(hipSetDevice(device_));
     if (!d.rgb || !last_dc || d.width == 0 || d.height == 0 || d.width > 65535 || d.height > 65535) return kErrArg;
     if (mode_ != 420) return kErrArg;  // stripes are S420_m (the reference's subsampling)
-    if (fmt_planes(fmt_) != 1) return kErrArg;  // and interleaved (the stripe pointer is one row of pixels)
+    if (fmt_planes(fmt_) != 1 || fmt_gray(fmt_)) return kErrArg;  // and interleaved colour (the stripe pointer is one row of pixels)
     if (d.maxval < 1 || d.maxval > 255) return kErrRange;
     const uint32_t mh_img = (d.height + 15) / 16;
     if (d.mcu_rows == 0 || d.mcu_row0 >= mh_img || d.mcu_rows > mh_img - d.mcu_row0) return kErrArg;

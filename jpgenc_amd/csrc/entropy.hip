@@ -866,7 +866,8 @@ __global__ __launch_bounds__(kK3Threads) void entropy_pack_kernel(FrameSet<Entro
 // codes >= 2 bits (a DC code and an EOB or AC code, each >= 1 bit), so each
 // workgroup's stream holds >= 128 bits and its first and last 8 bits, which the
 // placement reads, are defined.  Restart intervals of R MCUs: segments of bpm*R
-// blocks (>= 3 blocks, >= 6 bits; each starts byte-aligned), each cut into
+// blocks (>= 3 blocks, >= 6 bits; one component: >= 1 block, >= 2 bits; each starts
+// byte-aligned, and its placement reads no bits but its own), each cut into
 // balanced tiles of <= 128 blocks, a whole number of workgroups per segment.
 SegLayout seg_layout(const Geometry& g, uint32_t restart_mcus, uint32_t wgs_override) {
     SegLayout L;

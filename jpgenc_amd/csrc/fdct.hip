@@ -172,12 +172,15 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
 #define JPGE_K1_SHAPE 0
 #endif
 constexpr int kShape = JPGE_K1_SHAPE;
-static_assert(kShape >= kShapeRgb8 && kShape <= kShapeYuv444, "JPGE_K1_SHAPE");
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapeGray, "JPGE_K1_SHAPE");
 // The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
 // layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
 // conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
 // takes each cell's top-left word: no chroma filter.  maxval is 255 (kExact instances only).
+// The gray shape stages words that hold Y alone and has the row-8 kernel's one-component
+// instance only: 16 one-block MCUs per tile, the two Y rounds, no chroma rounds.
 constexpr bool kYuv = kShape >= kShapeNv12;
+constexpr bool kGray = kShape == kShapeGray;
 constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420;
 constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
 constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
@@ -232,6 +235,12 @@ __device__ __forceinline__ void unpack_yuv420(const uint4& v0, const uint4& v1, 
         }
     }
 }
+// The gray shape's run: the load's 16 bytes, one per staged word.
+__device__ __forceinline__ void unpack_gray(const uint4& v0, uint32_t px[16]) {
+    const uint32_t y[4] = {v0.x, v0.y, v0.z, v0.w};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) px[i] = __builtin_amdgcn_perm(0u, y[i >> 2], 0x0C0C0C00u | (uint32_t)(i & 3));
+}
 // a staged word's samples (exact: integers)
 __device__ __forceinline__ double yuv_y(uint32_t p) { return (double)(p & 0xFF) - 128.0; }
 __device__ __forceinline__ double yuv_c(uint32_t p, int comp) { return (double)((p >> (8 * comp)) & 0xFF) - 128.0; }
@@ -243,7 +252,9 @@ __device__ __forceinline__ uint32_t edge_yuv(const uint8_t* base, uint64_t strid
                                              uint32_t sy, uint32_t sx) {
     const uint32_t yv = base[(uint64_t)sy * stride + sx];
     const uint8_t* c = base + plane_stride;
-    if constexpr (kShape == kShapeNv12) {
+    if constexpr (kGray) {
+        return yv;
+    } else if constexpr (kShape == kShapeNv12) {
         c += (uint64_t)(sy >> 1) * stride + 2 * (uint64_t)(sx >> 1);
         return yv | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16);
     } else if constexpr (kShape == kShapeI420) {
@@ -275,7 +286,7 @@ __device__ __forceinline__ uint32_t edge_pixel(const uint8_t* rgb, uint64_t stri
 // inside their row, so the range is the last row's end.
 struct RgbRsrc {
     __amdgpu_buffer_rsrc_t p0;
-#if JPGE_K1_SHAPE >= 3
+#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7
     __amdgpu_buffer_rsrc_t p1, p2;  // (NV12: p2 repeats p1, unused)
 #endif
 };
@@ -318,6 +329,8 @@ __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff, 0, 0));
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, coff, 0, 0));
+#elif JPGE_K1_SHAPE == 7
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
 #else
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
@@ -340,7 +353,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || kYuv) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -676,7 +689,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || kYuv) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -686,8 +699,9 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     }
     constexpr int kK1Threads = kWaves * 64;
     constexpr uint32_t kMcus = 16 / kYh;            // MCUs per tile
-    constexpr int kBpm = kYh + 2;                   // blocks per MCU
-    constexpr int kRounds = 2 + 4 / kYh;            // 2 Y rounds + the chroma rounds
+    static_assert(!kGray || kYh == 1, "one component: one-block MCUs");
+    constexpr int kBpm = kGray ? 1 : kYh + 2;         // blocks per MCU
+    constexpr int kRounds = kGray ? 2 : 2 + 4 / kYh;  // 2 Y rounds + the chroma rounds (one component: none)
     __shared__ K1Lds<kWaves> lds;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     K1WaveLds& W = lds.w[wv];
@@ -769,7 +783,9 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
 
         uint32_t px[16];
-        if constexpr (kShape == kShapeX4 || kShape == kShapePlanar || kShape == kShapeYuv444) {
+        if constexpr (kGray) {
+            unpack_gray(c0, px);
+        } else if constexpr (kShape == kShapeX4 || kShape == kShapePlanar || kShape == kShapeYuv444) {
             unpack_run(c0, c1, c2, c3, sel4_, px);
         } else {
             const uint4 v0 = c0, v1 = c1, v2 = c2;
@@ -917,7 +933,11 @@ template <int kN>
 static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     const FdctArgs& a = fs.a[0];
     // the kernels assume these shapes (kernels.hpp Geometry)
-    if constexpr (kYuv420) {
+    if constexpr (kGray) {
+        // one component: one-block MCUs, whatever the subsampling mode
+        if (!a.g.gray() || a.g.yh != 1) return hipErrorInvalidValue;
+        return launch_row8<1, kN>(fs, grid, s, t);
+    } else if constexpr (kYuv420) {
         // the chroma planes are the S420_m planes already: the instance that takes each 2x2
         // cell's first staged word (all four hold the cell's sample) applies no filter
         if (a.g.row8() || a.g.yh != 2 || a.g.bpm != 6 || a.g.cfilt != kFiltS420m) return hipErrorInvalidValue;
@@ -943,7 +963,7 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
 }
 
 #if JPGE_K1_SHAPE != 0
-// this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444)
+// this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
@@ -954,6 +974,7 @@ hipError_t launch_fdct_planar(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t gr
 hipError_t launch_fdct_nv12(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_i420(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_yuv444(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_gray(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 
 uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs) {
     const uint32_t tiles = k1_tiles(g);
@@ -978,7 +999,10 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         // (a 16384^2 frame needs 805 MB of each)
         // (planar: each plane has its own descriptor, so the extent is one plane's)
         // (the 4:2:0 layouts' chroma planes have descriptors of their own, with smaller extents)
-        if (!fmt_valid(m.fmt) || m.g.height == 0 || (fmt_yuv(m.fmt) && m.maxval != 255)) return hipErrorInvalidValue;
+        // (a one-component geometry goes with the gray layout, and only with it)
+        if (!fmt_valid(m.fmt) || m.g.height == 0 || ((fmt_yuv(m.fmt) || fmt_gray(m.fmt)) && m.maxval != 255) ||
+            fmt_gray(m.fmt) != m.g.gray())
+            return hipErrorInvalidValue;
         const uint64_t row = fmt_row_bytes(m.fmt, m.g.width);
         const uint64_t extent = m.stride * (m.g.height - 1) + row;  // the descriptor's range
         if (m.stride < row || extent >= kOob || (uint64_t)m.stride * m.g.height >= kOob ||
@@ -1002,6 +1026,7 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         case kShapeNv12: return launch_fdct_nv12(w, grid, s, t);
         case kShapeI420: return launch_fdct_i420(w, grid, s, t);
         case kShapeYuv444: return launch_fdct_yuv444(w, grid, s, t);
+        case kShapeGray: return launch_fdct_gray(w, grid, s, t);
         default: return launch_fdct_planar(w, grid, s, t);
     }
 }

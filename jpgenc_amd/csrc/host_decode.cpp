@@ -184,6 +184,7 @@ int jpge_decode_coeffs(const uint8_t* jpg, size_t len, jpge_decoded* info, int16
     uint32_t restart = 0;
     size_t pos = 2;
     bool sof = false;
+    int ncomp = 3;  // components of the frame: 3, or 1 (a grayscale stream)
     for (;;) {  // header segments up to SOS (JpegSegments.hpp:55-358)
         if (pos + 4 > len || jpg[pos] != 0xFF) return JPGE_E_FORMAT;
         const uint8_t m = jpg[pos + 1];
@@ -196,10 +197,12 @@ int jpge_decode_coeffs(const uint8_t* jpg, size_t len, jpge_decoded* info, int16
                 for (int i = 0; i < 64; ++i) qt[id][jpge::kZigzagToNatural[i]] = s[o + 1 + i];
             }
         } else if (m == 0xC0) {  // SOF0
-            if (sl < 17 || s[0] != 8 || s[5] != 3) return JPGE_E_FORMAT;
+            if (sl < 11 || s[0] != 8 || (s[5] != 3 && s[5] != 1)) return JPGE_E_FORMAT;
+            ncomp = s[5];
+            if (sl < (uint32_t)(8 + 3 * ncomp)) return JPGE_E_FORMAT;
             info->height = be16(s + 1);
             info->width = be16(s + 3);
-            for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < ncomp; ++c) {
                 hs[c] = s[7 + 3 * c] >> 4;
                 vs[c] = s[7 + 3 * c] & 15;
                 tq[c] = s[8 + 3 * c] & 3;
@@ -218,9 +221,9 @@ int jpge_decode_coeffs(const uint8_t* jpg, size_t len, jpge_decoded* info, int16
         } else if (m == 0xDD) {  // DRI
             if (sl < 4) return JPGE_E_FORMAT;
             restart = be16(s);
-        } else if (m == 0xDA) {  // SOS: three components, in frame order
-            if (!sof || sl < 2 + 1 + 2 * 3 + 3 || s[0] != 3) return JPGE_E_FORMAT;
-            for (int c = 0; c < 3; ++c) {
+        } else if (m == 0xDA) {  // SOS: the frame's components (three, or the one), in frame order
+            if (!sof || sl < (uint32_t)(2 + 1 + 2 * ncomp + 3) || s[0] != ncomp) return JPGE_E_FORMAT;
+            for (int c = 0; c < ncomp; ++c) {
                 td[c] = s[2 + 2 * c] >> 4;
                 ta[c] = s[2 + 2 * c] & 15;
                 if (td[c] > 3 || ta[c] > 3) return JPGE_E_FORMAT;
@@ -232,23 +235,27 @@ int jpge_decode_coeffs(const uint8_t* jpg, size_t len, jpge_decoded* info, int16
         }
         pos += 2 + sl;
     }
-    // the sampling shapes jpge emits: chroma 1x1, Y yh x yv
+    // the sampling shapes jpge emits: chroma 1x1, Y yh x yv; one component: 1x1 (its
+    // non-interleaved scan's MCU is one block whatever the factors, T.81 A.2.2)
+    const bool gray = ncomp == 1;
     const int yh = hs[0], yv = vs[0];
-    if (hs[1] != 1 || vs[1] != 1 || hs[2] != 1 || vs[2] != 1 || yh < 1 || yh > 4 || yv < 1 || yv > 2 ||
+    if (gray) {
+        if (yh != 1 || yv != 1 || !info->width || !info->height) return JPGE_E_FORMAT;
+    } else if (hs[1] != 1 || vs[1] != 1 || hs[2] != 1 || vs[2] != 1 || yh < 1 || yh > 4 || yv < 1 || yv > 2 ||
         yh * yv > 4 || !info->width || !info->height)
         return JPGE_E_FORMAT;
-    for (int c = 0; c < 3; ++c)
+    for (int c = 0; c < ncomp; ++c)
         if (!dc[td[c]].ok || !ac[ta[c]].ok) return JPGE_E_FORMAT;
     const uint32_t mw = (info->width + 8 * yh - 1) / (8 * yh), mh = (info->height + 8 * yv - 1) / (8 * yv);
     info->yh = (uint32_t)yh;
     info->yv = (uint32_t)yv;
     info->restart = restart;
     info->y_blocks = (size_t)mw * yh * mh * yv;
-    info->c_blocks = (size_t)mw * mh;
+    info->c_blocks = gray ? 0 : (size_t)mw * mh;
     std::memcpy(info->qy, qt[tq[0]], 64);
-    std::memcpy(info->qc, qt[tq[1]], 64);
+    if (!gray) std::memcpy(info->qc, qt[tq[1]], 64);  // (one component: qc stays zero)
     if (!y) return JPGE_OK;  // size query
-    if (!cb || !cr || cap_y_blocks < info->y_blocks || cap_c_blocks < info->c_blocks) return JPGE_E_NOSPACE;
+    if ((!gray && (!cb || !cr)) || cap_y_blocks < info->y_blocks || cap_c_blocks < info->c_blocks) return JPGE_E_NOSPACE;
 
     BitReader br(jpg, len, pos);
     int pred[3] = {0, 0, 0};
@@ -286,6 +293,7 @@ int jpge_decode_coeffs(const uint8_t* jpg, size_t len, jpge_decoded* info, int16
         for (int v = 0; v < yv; ++v)
             for (int u = 0; u < yh; ++u)
                 if (!block(0, y + ((size_t)(i * yv + v) * ybw + j * yh + u) * 64)) return JPGE_E_FORMAT;
+        if (gray) continue;  // (cb, cr are not written)
         if (!block(1, cb + (size_t)m * 64) || !block(2, cr + (size_t)m * 64)) return JPGE_E_FORMAT;
     }
     // the stream ends with the 1-filled final byte and EOI

@@ -182,13 +182,14 @@ void quality_tables(int q, uint8_t qy[64], uint8_t qc[64]) {
     }
 }
 
+// sSOI + sAPP0 (JpegSegments.hpp:55-109): JFIF 1.1, no units, density 1x1.
+static const uint8_t kSoiApp0[20] = {0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F',
+                                     0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00};
+
 std::vector<uint8_t> jfif_headers(uint32_t rw, uint32_t rh, const uint8_t qy[64], const uint8_t qc[64],
                                   const HuffTable* const tables[4], uint32_t restart_mcus, uint8_t ysamp) {
     std::vector<uint8_t> o;
     o.reserve(700);
-    // sSOI + sAPP0 (JpegSegments.hpp:55-109): JFIF 1.1, no units, density 1x1.
-    static const uint8_t kSoiApp0[20] = {0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F',
-                                         0x00, 0x01, 0x01, 0x00, 0x00, 0x01, 0x00, 0x01, 0x00, 0x00};
     o.insert(o.end(), kSoiApp0, kSoiApp0 + 20);
     // sDQT x2 (JpegSegments.hpp:259-319): one table per segment, zig-zag order.
     const uint8_t* qt[2] = {qy, qc};
@@ -217,6 +218,34 @@ std::vector<uint8_t> jfif_headers(uint32_t rw, uint32_t rh, const uint8_t qy[64]
     // sSOS (JpegSegments.hpp:322-358): Y tables 0/0, Cb and Cr 1/1, Ss 0 Se 63 AhAl 0.
     static const uint8_t kSos[14] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00};
     o.insert(o.end(), kSos, kSos + 14);
+    return o;
+}
+
+std::vector<uint8_t> jfif_headers_gray(uint32_t rw, uint32_t rh, const uint8_t qy[64],
+                                       const HuffTable* const tables[2], uint32_t restart_mcus) {
+    // SOI, APP0 and the luma DQT as in jfif_headers; SOF0, the two DHTs and SOS for one
+    // component (1x1, quantiser 0, tables 0/0)
+    std::vector<uint8_t> o;
+    o.reserve(400);
+    o.insert(o.end(), kSoiApp0, kSoiApp0 + 20);
+    o.push_back(0xFF); o.push_back(0xDB); put16(o, 67); o.push_back(0);
+    for (int i = 0; i < 64; ++i) o.push_back(qy[kZigzagToNatural[i]]);
+    o.push_back(0xFF); o.push_back(0xC0); put16(o, 11); o.push_back(8);
+    put16(o, rh & 0xFFFF); put16(o, rw & 0xFFFF);
+    const uint8_t comp[4] = {1, 1, 0x11, 0};
+    o.insert(o.end(), comp, comp + 4);
+    static const uint8_t kInfo[2] = {0x00, 0x10};
+    for (int k = 0; k < 2; ++k) {
+        const HuffTable& t = *tables[k];
+        o.push_back(0xFF); o.push_back(0xC4); put16(o, (uint32_t)(2 + 17 + t.nsym)); o.push_back(kInfo[k]);
+        for (int l = 1; l <= 16; ++l) o.push_back(t.bits[l]);
+        o.insert(o.end(), t.huffval, t.huffval + t.nsym);
+    }
+    if (restart_mcus) {
+        o.push_back(0xFF); o.push_back(0xDD); put16(o, 4); put16(o, restart_mcus & 0xFFFF);
+    }
+    static const uint8_t kSos[10] = {0xFF, 0xDA, 0x00, 0x08, 0x01, 0x01, 0x00, 0x00, 0x3F, 0x00};
+    o.insert(o.end(), kSos, kSos + 10);
     return o;
 }
 

@@ -58,6 +58,12 @@ extern const uint8_t kZigzagToNatural[64];
 std::vector<uint8_t> jfif_headers(uint32_t real_width, uint32_t real_height, const uint8_t qy[64],
                                   const uint8_t qc[64], const HuffTable* const tables[4], uint32_t restart_mcus = 0,
                                   uint8_t ysamp = 0x22);
+// The one-component (grayscale) stream's headers: SOI, APP0, DQT(luma), SOF0 with the one
+// component 1x1 on table 0, DHT x2 (tables[0] Y-DC, tables[1] Y-AC), DRI if restart_mcus > 0
+// (the interval counts blocks: a non-interleaved scan's MCU is one block, ITU T.81 A.2.2),
+// and a one-component SOS.
+std::vector<uint8_t> jfif_headers_gray(uint32_t real_width, uint32_t real_height, const uint8_t qy[64],
+                                       const HuffTable* const tables[2], uint32_t restart_mcus = 0);
 
 // Deterministic synthetic RGB8 frame (integer-only, identical on every host):
 // kind 0 = smooth gradients + texture + noise (photo-like), 1 = uniform random

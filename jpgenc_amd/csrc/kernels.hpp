@@ -28,6 +28,8 @@ namespace jpge {
 // An MCU is yh x yv Y blocks (row by row) + one Cb + one Cr block, bpm = yh*yv + 2:
 //   4:2:0 (the reference's S420_m, and the S420 / S420_lm filters): 2x2, 16x16 px;
 //   4:4:4: 1x1, 8x8 px;  4:2:2: 2x1, 16x8 px;  4:1:1: 4x1, 32x8 px.
+// One component (kFmtGray8): bpm = 1 with yh = 1, an MCU is one block and there is no
+// chroma; blocks, the DC chain and the texts run in block raster order.
 // cfilt selects the 4:2:0 chroma filter of applySubsampling (Image.cpp:279-306).
 constexpr uint32_t kFiltS420m = 0, kFiltS420lm = 1, kFiltS420 = 2;
 struct Geometry {
@@ -38,14 +40,17 @@ struct Geometry {
     uint32_t cfilt = kFiltS420m;
     JPGE_HD uint32_t nmcu() const { return mw * mh; }
     JPGE_HD uint32_t nblocks() const { return nmcu() * bpm; }
-    JPGE_HD uint32_t yv() const { return (bpm - 2) / yh; }  // Y blocks down an MCU (1, 2)
+    JPGE_HD bool gray() const { return bpm == 1; }          // one component: no chroma slots
+    JPGE_HD uint32_t ny() const { return gray() ? 1u : bpm - 2; }  // Y blocks of an MCU
+    JPGE_HD uint32_t yv() const { return ny() / yh; }  // Y blocks down an MCU (1, 2)
     JPGE_HD bool s444() const { return bpm == 3; }
-    JPGE_HD bool row8() const { return bpm - 2 == yh; }  // MCUs one block row high
+    JPGE_HD bool row8() const { return ny() == yh; }  // MCUs one block row high
     JPGE_HD uint32_t mcu_w() const { return 8 * yh; }   // MCU size in pixels
     JPGE_HD uint32_t mcu_h() const { return 8 * yv(); }
 };
-// component of MCU slot k: 0 = Y, 1 = Cb, 2 = Cr (the last two slots are the chroma)
-JPGE_HD inline int block_comp(int k, uint32_t bpm) { return k < (int)bpm - 2 ? 0 : k - ((int)bpm - 3); }
+// component of MCU slot k: 0 = Y, 1 = Cb, 2 = Cr (the last two slots are the chroma;
+// bpm = 1: the one slot is Y)
+JPGE_HD inline int block_comp(int k, uint32_t bpm) { return bpm == 1 || k < (int)bpm - 2 ? 0 : k - ((int)bpm - 3); }
 
 // Input layouts (jpge.h JPGE_FMT_*, the same values) and K1's load shapes: what a lane
 // loads for its 16-pixel run.  Each shape is one build of fdct.hip (JPGE_K1_SHAPE).
@@ -54,7 +59,13 @@ constexpr int kFmtRgb8 = 0, kFmtBgr8 = 1, kFmtRgba8 = 2, kFmtBgra8 = 3, kFmtRgb8
 // NV12 (Y plane + one plane of interleaved Cb,Cr at half size), I420 (Y, Cb, Cr planes,
 // chroma at half size), planar 4:4:4 (addressed as kFmtRgb8Planar)
 constexpr int kFmtNv12 = 16, kFmtI420 = 17, kFmtYuv444Planar = 18;
-JPGE_HD inline bool fmt_valid(int fmt) { return (fmt >= 0 && fmt < kFmtCount) || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar); }
+// one plane of 8-bit luminance samples (a sample v is the fp64 value v - 128, as a Y sample
+// above): a one-component stream, Geometry::gray(), whatever the subsampling mode
+constexpr int kFmtGray8 = 8;
+JPGE_HD inline bool fmt_valid(int fmt) {
+    return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar);
+}
+JPGE_HD inline bool fmt_gray(int fmt) { return fmt == kFmtGray8; }
 JPGE_HD inline bool fmt_yuv(int fmt) { return fmt >= kFmtNv12; }
 JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420; }  // chroma planes at half size
 constexpr int kShapeRgb8 = 0;    // 48 bytes R,G,B,...: three b128 loads
@@ -64,12 +75,13 @@ constexpr int kShapePlanar = 3;  // 16 bytes of each of the planes R, G, B: thre
 constexpr int kShapeNv12 = 4;    // 16 Y bytes + the 16 Cb,Cr bytes (8 samples of both) under them: two b128 loads
 constexpr int kShapeI420 = 5;    // 16 Y bytes + 16 Cb bytes + 16 Cr bytes (the lane uses 8 of each): three b128 loads
 constexpr int kShapeYuv444 = 6;  // the planar shape's loads of the planes Y, Cb, Cr
+constexpr int kShapeGray = 7;    // 16 Y bytes: one b128 load (no chroma: Geometry::gray())
 JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
+    return fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
          : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
 }
 // bytes per pixel within a row (planar: of one plane), and planes
-JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
+JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
 JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt == kFmtNv12 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
 // The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
 // that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs).

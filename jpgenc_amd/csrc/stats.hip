@@ -80,7 +80,10 @@ struct K2WLds {
     uint32_t next;                                       // the next sub-stream to take
 };
 
-template <int kN>
+// kGray: the one-component instance (Geometry::gray(): an MCU is one block, no chroma; the
+// chain, the text and the keys run in block order).  The three-component instance is the
+// code it was before that instance existed.
+template <int kN, bool kGray>
 __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe))) void stats_wave_kernel(FrameSet<StatsArgs, kN> fs) {
     const uint32_t set_f = (kN == 1 ? 0u : set_member_rolled(fs.wg0, fs.n, blockIdx.x));  // (frame sets: kernels.hpp)
     const StatsArgs& a = fs.a[set_f];
@@ -89,7 +92,8 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    const uint32_t bpm = a.g.bpm, mw = a.g.mw, yh = a.g.yh, yv = a.g.yv();
+    const uint32_t bpm = kGray ? 1u : a.g.bpm, mw = a.g.mw, yh = kGray ? 1u : a.g.yh;
+    const uint32_t yv = kGray ? 1u : (bpm - 2) / yh;
     const uint32_t yhs = (uint32_t)__builtin_ctz(yh);
     const uint32_t ybw = mw * yh;  // Y blocks per block row
     const uint32_t S = seg_tiles(a.seg) * kRecSub;
@@ -191,7 +195,7 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
         const uint32_t g = b0 + (uint32_t)lane;
         const uint32_t m6 = g / bpm, k = g - m6 * bpm;
         const uint32_t mrow = m6 / mw, mcol = m6 - mrow * mw;
-        const int comp = block_comp((int)k, bpm);
+        const int comp = kGray ? 0 : ((int)k < (int)bpm - 2 ? 0 : (int)k - ((int)bpm - 3));  // (block_comp)
         // text index (the Y text in block raster order; all Cr after all Cb), relative to the bases
         const uint32_t rel = comp == 0 ? (mrow * yv + (k >> yhs)) * ybw + mcol * yh + (k & (yh - 1)) - ybase
                                        : (m6 - cbase) | (comp == 2 ? 0x80000000u : 0u);
@@ -203,13 +207,15 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
         const uint32_t acb = (rel & 0x80000000u) | ((rel & 0x7FFFFFFFu) << 7) | tsel;
         // DC difference to the chain predecessor: the previous Y slot, 3 blocks back for an
         // MCU's first Y block, bpm back for chroma; none in the first MCU; restarts reset it
+        // (one component: the block before; none for the first block; every block of an
+        // interval's start resets)
         int dd;
         {
-            const bool ynext = k >= 1 && k < bpm - 2;
-            const int back = ynext ? 1 : (k == 0 ? 3 : (int)bpm);
+            const bool ynext = !kGray && k >= 1 && k < bpm - 2;
+            const int back = kGray || ynext ? 1 : (k == 0 ? 3 : (int)bpm);
             const bool none = !ynext && g < bpm;
             bool reset = false;
-            if (a.rst.mcus && (k == 0 || k >= bpm - 2)) reset = (m6 + a.rst.mcu0) % a.rst.mcus == 0;
+            if (a.rst.mcus && (kGray || k == 0 || k >= bpm - 2)) reset = (m6 + a.rst.mcu0) % a.rst.mcus == 0;
             const int dcv = __builtin_amdgcn_ds_bpermute((lane + 6) * 4, dcs);
             int pd = __builtin_amdgcn_ds_bpermute((lane + 6 - back) * 4, dcs);  // (lane - back >= -6)
             pd = reset ? 0 : none ? (comp == 0 ? a.seed.v[0] : comp == 1 ? a.seed.v[1] : a.seed.v[2]) : pd;
@@ -455,8 +461,12 @@ static hipError_t launch_stats_fs(const FrameSet<StatsArgs, kN>& fs, hipStream_t
         // (32-bit block numbers and buffer offsets)
         if ((uint64_t)fs.a[f].g.nblocks() * 128 >= (1ull << 32)) return hipErrorInvalidValue;
         if (fs.wg0[f + 1] - fs.wg0[f] != stats_grid(fs.a[f].seg, fs.a[f].wgs)) return hipErrorInvalidValue;
+        // (a set's members share a kernel instance; one component: bpm = 1 goes with yh = 1)
+        if (fs.a[f].g.gray() != fs.a[0].g.gray() || (fs.a[f].g.gray() && fs.a[f].g.yh != 1)) return hipErrorInvalidValue;
     }
-    return launch_timed(t, stats_wave_kernel<kN>, dim3(fs.wg0[fs.n]), dim3(kWThreads), s, fs);
+    if (fs.a[0].g.gray())
+        return launch_timed(t, stats_wave_kernel<kN, true>, dim3(fs.wg0[fs.n]), dim3(kWThreads), s, fs);
+    return launch_timed(t, stats_wave_kernel<kN, false>, dim3(fs.wg0[fs.n]), dim3(kWThreads), s, fs);
 }
 
 hipError_t launch_stats(const StatsArgs& a, hipStream_t s, const KTimer* t) {

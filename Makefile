@@ -25,8 +25,9 @@ FACADE_TEST := tests/cpp/bin/test_facade
 HUFF_TEST   := tests/cpp/bin/test_huffman_fast
 QUANT_TEST  := tests/cpp/bin/test_quant_fast
 EXIT_TEST   := tests/cpp/bin/test_exit_close
+HUFFSPEC_TEST := tests/cpp/bin/test_huffspec
 
-all: $(LIBDIR)/libjpge.so $(BINDIR)/jpgenc $(FACADE_TEST) $(HUFF_TEST) $(QUANT_TEST) $(EXIT_TEST) oracle
+all: $(LIBDIR)/libjpge.so $(BINDIR)/jpgenc $(FACADE_TEST) $(HUFF_TEST) $(QUANT_TEST) $(EXIT_TEST) $(HUFFSPEC_TEST) oracle
 
 # (fdct_*.hip: fdct.hip built per input load shape)
 K1_SHAPES := fdct_bgr8.o fdct_x4.o fdct_planar.o fdct_nv12.o fdct_i420.o fdct_yuv444.o fdct_gray.o
@@ -93,6 +94,12 @@ $(QUANT_TEST): tests/cpp/test_quant_fast.cpp $(SRC)/constants.hpp
 	@mkdir -p tests/cpp/bin
 	$(CXX) -O2 -std=c++17 -ffp-contract=off -I$(SRC) -o $@ $<
 
+# fixed Huffman tables: spec validation and canonical codes, host only
+# (tests/test_fixedhuff_cpu.py runs it)
+$(HUFFSPEC_TEST): tests/cpp/test_huffspec.cpp $(SRC)/host_io.cpp $(SRC)/host_io.hpp $(SRC)/huffman.hpp $(SRC)/host_par.hpp
+	@mkdir -p tests/cpp/bin
+	$(CXX) $(CXXFLAGS) -o $@ $< $(SRC)/host_io.cpp
+
 # Host code under AddressSanitizer + UndefinedBehaviorSanitizer (run by
 # tests/test_asan.py in the CPU suite): every host .cpp of the library rebuilt
 # sanitized and linked with the (unsanitized) HIP device objects, plus the host
@@ -101,7 +108,8 @@ ASAN_FLAGS := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-f
 ASAN_DIR   := build/asan
 ASAN_BIN   := tests/cpp/bin/asan
 ASAN_OBJS  := $(addprefix $(ASAN_DIR)/,$(HOST_SRCS:.cpp=.o))
-ASAN_TESTS := $(ASAN_BIN)/test_host_asan $(ASAN_BIN)/test_facade $(ASAN_BIN)/test_huffman_fast $(ASAN_BIN)/test_quant_fast
+ASAN_TESTS := $(ASAN_BIN)/test_host_asan $(ASAN_BIN)/test_facade $(ASAN_BIN)/test_huffman_fast $(ASAN_BIN)/test_quant_fast \
+              $(ASAN_BIN)/test_huffspec
 
 $(ASAN_DIR)/%.o: $(SRC)/%.cpp $(HEADERS)
 	@mkdir -p $(ASAN_DIR)
@@ -122,6 +130,10 @@ $(ASAN_BIN)/test_huffman_fast: tests/cpp/test_huffman_fast.cpp $(SRC)/huffman.cp
 $(ASAN_BIN)/test_quant_fast: tests/cpp/test_quant_fast.cpp $(SRC)/constants.hpp
 	@mkdir -p $(ASAN_BIN)
 	$(CXX) -std=c++17 -ffp-contract=off -I$(SRC) $(ASAN_FLAGS) -o $@ $<
+
+$(ASAN_BIN)/test_huffspec: tests/cpp/test_huffspec.cpp $(SRC)/host_io.cpp $(SRC)/host_io.hpp $(SRC)/huffman.hpp $(SRC)/host_par.hpp
+	@mkdir -p $(ASAN_BIN)
+	$(CXX) $(CXXFLAGS) $(ASAN_FLAGS) -o $@ $< $(SRC)/host_io.cpp
 
 asan: $(ASAN_TESTS)
 

@@ -65,7 +65,8 @@ typedef struct {
     float total;    /* K1 start .. K3 end of that frame (includes the queued work of other frames) */
     double fdct_sum, dc_stats_sum, entropy_sum; /* accumulated since jpge_reset_timing (ms) */
     uint64_t frames;                            /* frames accumulated */
-    uint64_t symbols; /* Huffman-coded symbols of those frames (= K2's 4-byte symbol records) */
+    uint64_t symbols; /* Huffman-coded symbols of those frames (= K2's 4-byte symbol records); counted from the
+                         histograms, so frames of a fixed Huffman mode (jpge_set_huffman) do not advance it */
     double code_sum, pack_sum; /* K3's entropy_code_kernel and entropy_pack_kernel alone (ms, accumulated) */
     uint64_t launches;         /* timed launches of each kernel (batches of small frames launch frame sets:
                                   one launch per kernel for up to 4 frames; the sums are per launch) */
@@ -188,6 +189,44 @@ int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride);
 /* bytes per pixel along a row and number of planes of a layout (host only; either
  * pointer may be NULL); unknown layout: JPGE_E_ARG */
 int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes);
+
+/* ---- Huffman tables of the output (an addition; replaces nothing in the reference) ----
+ * JPGE_HUFF_OPTIMAL builds per-image tables as writeJPEG does (Image.cpp:888-930): the
+ * reference's stream, bit-identical, and a device -> host -> device round trip in every
+ * frame (histograms out, tables back).  The fixed modes code with tables known before the
+ * frame arrives, as libjpeg without `optimize` and MJPEG cameras do: a few per cent more
+ * bytes, and no host work between a frame's statistics and entropy kernels. */
+#define JPGE_HUFF_OPTIMAL  0   /* per-image tables, the reference's stream (default) */
+#define JPGE_HUFF_STANDARD 1   /* ITU T.81 Annex K tables K.3-K.6 */
+#define JPGE_HUFF_CUSTOM   2   /* caller's tables */
+/* A table in DHT form (ITU T.81 B.2.4.2): bits[l - 1] = number of codes of length l
+ * (1..16), huffval = the symbols in order of increasing code length; codes are assigned
+ * canonically (T.81 Annex C).  (An addition; replaces nothing in the reference.) */
+typedef struct { uint8_t bits[16]; uint8_t huffval[256]; } jpge_huff_spec;
+/* Huffman mode of the context's following jpge_encode_rgb8, jpge_encode_batch and
+ * jpge_encode_file(s) calls (an output property: the PPM entries honour it), also on a
+ * group member's context (jpge_group_context), and so for jpge_group_encode_batch.  specs:
+ * Y-DC, Y-AC, C-DC, C-AC; read only for JPGE_HUFF_CUSTOM (a one-component stream uses
+ * specs 0 and 1 and writes two DHT segments).  JPGE_E_ARG for an unknown mode, CUSTOM with
+ * specs == NULL, and a spec with more than 256 symbols, a repeated symbol, a Kraft sum
+ * (sum of bits[l - 1] * 2^(16 - l)) of 2^16 or more (a code of all ones, T.81 C.2), or one
+ * that is incomplete for 8-bit baseline data: a DC table must hold categories 0..11, an AC
+ * table 0x00, 0xF0 and every run 0..15 x size 1..10 (in a fixed mode no frame's symbols
+ * are looked at before they are coded, so no symbol may lack a code).  The setting is
+ * orthogonal to the subsampling mode, the restart interval, the input layout, frame sets
+ * and lanes.  The segment order is unchanged, each DHT carries the table as given, and
+ * every other header byte is the optimal mode's.  In a fixed mode jpge_stripe_*,
+ * jpge_group_encode_striped and jpge_encode_planes return JPGE_E_ARG (stripes share one
+ * image's tables through the histogram all-reduce); the stage entries (jpge_fdct_quant,
+ * jpge_symbol_stats, ...) behave the same in every mode; jpge_timing.symbols does not
+ * advance (its source is the histogram).  (An addition; replaces nothing in the reference.) */
+int jpge_set_huffman(jpge_ctx* ctx, int mode, const jpge_huff_spec specs[4]);
+/* The current mode and, in a fixed mode, its four tables (specs may be NULL;
+ * JPGE_HUFF_OPTIMAL fills nothing).  (An addition; replaces nothing in the reference.) */
+int jpge_get_huffman(jpge_ctx* ctx, int* mode, jpge_huff_spec specs[4]);
+/* Annex K table 0 Y-DC (K.3), 1 Y-AC (K.5), 2 C-DC (K.4), 3 C-AC (K.6); host only.
+ * (An addition; replaces nothing in the reference.) */
+int jpge_standard_huffman(int table /*0..3*/, jpge_huff_spec* spec);
 
 /* Worst-case .jpg size for a frame, in any subsampling mode (header + 2x
  * worst-case entropy + RST markers + EOI). */

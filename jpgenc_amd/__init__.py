@@ -34,6 +34,10 @@ _FMT_420 = (JPGE_FMT_NV12, JPGE_FMT_I420)
 #: chroma table and the subsampling mode do not enter
 JPGE_FMT_GRAY8 = 8
 
+#: Huffman modes (jpge.h JPGE_HUFF_*): per-image tables (the reference's stream, the default),
+#: the ITU T.81 Annex K tables, or the caller's four tables
+JPGE_HUFF_OPTIMAL, JPGE_HUFF_STANDARD, JPGE_HUFF_CUSTOM = 0, 1, 2
+
 #: subsampling modes (jpge.h JPGE_S*) -> (Y blocks across, Y blocks down) an MCU
 SUBSAMPLING = {420: (2, 2), 4200: (2, 2), 4201: (2, 2), 444: (1, 1), 422: (2, 1), 411: (4, 1)}
 
@@ -48,6 +52,7 @@ EXPORTS = (
     "jpge_strerror", "jpge_version", "jpge_device_count", "jpge_open", "jpge_open_ex", "jpge_close", "jpge_set_timing",
     "jpge_get_timing", "jpge_reset_timing", "jpge_get_lanes", "jpge_set_restart_interval", "jpge_set_subsampling",
     "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info",
+    "jpge_set_huffman", "jpge_get_huffman", "jpge_standard_huffman",
     "jpge_max_jpeg_bytes", "jpge_quality_tables", "jpge_encode_rgb8", "jpge_encode_batch",
     "jpge_fdct_quant", "jpge_symbol_stats", "jpge_huffman_table", "jpge_huffman_text", "jpge_parse_ppm",
     "jpge_ppm_info", "jpge_encode_file", "jpge_encode_files", "jpge_synth_rgb8", "jpge_arai_constants",
@@ -105,6 +110,29 @@ class Decoded(ctypes.Structure):
                 ("c_blocks", ctypes.c_size_t), ("qy", ctypes.c_uint8 * 64), ("qc", ctypes.c_uint8 * 64)]
 
 
+class HuffSpec(ctypes.Structure):
+    """jpge_huff_spec: a Huffman table in DHT form (codes per length 1..16, then the symbols)."""
+    _fields_ = [("bits", ctypes.c_uint8 * 16), ("huffval", ctypes.c_uint8 * 256)]
+
+    def as_tuple(self) -> tuple[list[int], list[int]]:
+        bits = [int(b) for b in self.bits]
+        return bits, [int(v) for v in self.huffval[:min(256, sum(bits))]]
+
+    @classmethod
+    def from_tuple(cls, t):
+        """(bits, huffval): 16 counts and the symbols (at most 256 are kept; a longer
+        list still counts in bits, so the library rejects it)."""
+        bits, vals = t
+        if len(bits) != 16:
+            raise ValueError("a Huffman spec has 16 code-length counts")
+        s = cls()
+        for i, b in enumerate(bits):
+            s.bits[i] = int(b)
+        for i, v in enumerate(list(vals)[:256]):
+            s.huffval[i] = int(v)
+        return s
+
+
 class Timing(ctypes.Structure):
     _fields_ = [("fdct", ctypes.c_float), ("dc_stats", ctypes.c_float), ("entropy", ctypes.c_float),
                 ("total", ctypes.c_float), ("fdct_sum", ctypes.c_double), ("dc_stats_sum", ctypes.c_double),
@@ -140,6 +168,9 @@ def lib() -> ctypes.CDLL:
         L.jpge_set_input_format.argtypes = [vp, i32, sz]
         L.jpge_get_input_format.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(sz)]
         L.jpge_input_format_info.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.jpge_set_huffman.argtypes = [vp, i32, ctypes.POINTER(HuffSpec)]
+        L.jpge_get_huffman.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(HuffSpec)]
+        L.jpge_standard_huffman.argtypes = [i32, ctypes.POINTER(HuffSpec)]
         L.jpge_device_count.argtypes = [ctypes.POINTER(i32)]
         L.jpge_max_jpeg_bytes.restype = sz
         L.jpge_max_jpeg_bytes.argtypes = [u32, u32]
@@ -411,6 +442,22 @@ def input_format_info(fmt: int) -> tuple[int, int]:
     return b.value, n.value
 
 
+def standard_huffman(table: int) -> tuple[list[int], list[int]]:
+    """ITU T.81 Annex K table 0 Y-DC, 1 Y-AC, 2 C-DC, 3 C-AC as (bits, huffval): the
+    number of codes of each length 1..16, and the symbols in DHT order; host only."""
+    s = HuffSpec()
+    _check(lib().jpge_standard_huffman(int(table), ctypes.byref(s)), "standard_huffman")
+    return s.as_tuple()
+
+
+def _huff_specs(specs):
+    if specs is None:
+        return None
+    if len(specs) != 4:
+        raise ValueError("four Huffman specs: Y-DC, Y-AC, C-DC, C-AC")
+    return (HuffSpec * 4)(*[HuffSpec.from_tuple(t) for t in specs])
+
+
 class Yuv420Frame(np.ndarray):
     """A host NV12 or I420 frame (pack_yuv420): the layout's bytes, planes back to back
     (plane stride 0), with the geometry that a flat buffer does not show."""
@@ -598,6 +645,23 @@ class Encoder:
         f, ps = ctypes.c_int32(), ctypes.c_size_t()
         _check(lib().jpge_get_input_format(self._ctx, ctypes.byref(f), ctypes.byref(ps)), "get_input_format")
         return f.value, ps.value
+
+    def set_huffman(self, mode: int, specs=None) -> None:
+        """Huffman tables of the following encodes (encode*, encode_tensor*, encode_file(s)):
+        JPGE_HUFF_OPTIMAL (per-image tables, the reference's stream; the default),
+        JPGE_HUFF_STANDARD (ITU T.81 Annex K) or JPGE_HUFF_CUSTOM with specs = four
+        (bits, huffval) tables, Y-DC, Y-AC, C-DC, C-AC (as standard_huffman returns them).
+        A fixed mode has no host work between a frame's kernels; the stripe phases and
+        encode_planes refuse it."""
+        _check(lib().jpge_set_huffman(self._ctx, int(mode), _huff_specs(specs)), "set_huffman")
+
+    def huffman(self):
+        """(mode, specs): the Huffman mode and, in a fixed mode, its four (bits, huffval)
+        tables (None with JPGE_HUFF_OPTIMAL)."""
+        m = ctypes.c_int32()
+        arr = (HuffSpec * 4)()
+        _check(lib().jpge_get_huffman(self._ctx, ctypes.byref(m), arr), "get_huffman")
+        return m.value, ([a.as_tuple() for a in arr] if m.value else None)
 
     def lanes(self) -> int:
         n = ctypes.c_int32()
@@ -993,6 +1057,15 @@ class Group:
             _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
             _check(lib().jpge_set_input_format(c, int(fmt), int(plane_stride)), "set_input_format")
         self._fmt = int(fmt)
+
+    def set_huffman(self, mode: int, specs=None) -> None:
+        """Huffman mode of every member's context (Encoder.set_huffman): for encode_batch;
+        encode_striped needs JPGE_HUFF_OPTIMAL."""
+        arr = _huff_specs(specs)
+        for m in range(self.size()[0]):
+            c = ctypes.c_void_p()
+            _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
+            _check(lib().jpge_set_huffman(c, int(mode), arr), "set_huffman")
 
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         """Config 4: frame i on member i mod N."""

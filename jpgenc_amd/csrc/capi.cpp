@@ -279,6 +279,27 @@ int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride) {
     return JPGE_OK;
 }
 
+static_assert(sizeof(jpge_huff_spec) == sizeof(jpge::HuffSpec) && sizeof(jpge_huff_spec) == 272, "Huffman spec layout");
+
+int jpge_set_huffman(jpge_ctx* ctx, int mode, const jpge_huff_spec specs[4]) {
+    CtxUse use(ctx);
+    if (!use) return JPGE_E_ARG;
+    return ctx->enc->set_huffman(mode, reinterpret_cast<const jpge::HuffSpec*>(specs)) ? JPGE_E_ARG : JPGE_OK;
+}
+
+int jpge_get_huffman(jpge_ctx* ctx, int* mode, jpge_huff_spec specs[4]) {
+    CtxUse use(ctx);
+    if (!use || !mode) return JPGE_E_ARG;
+    ctx->enc->huffman(mode, reinterpret_cast<jpge::HuffSpec*>(specs));
+    return JPGE_OK;
+}
+
+int jpge_standard_huffman(int table, jpge_huff_spec* spec) {
+    if (table < 0 || table > 3 || !spec) return JPGE_E_ARG;
+    std::memcpy(spec, &jpge::kAnnexKHuffman[table], sizeof(*spec));
+    return JPGE_OK;
+}
+
 int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes) {
     if (!jpge::fmt_valid(format)) return JPGE_E_ARG;
     if (bytes_per_pixel) *bytes_per_pixel = (int)jpge::fmt_bpp(format);

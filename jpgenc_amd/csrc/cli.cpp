@@ -5,7 +5,10 @@
 //   --gpus N / --devices a,b,...   one image row-striped over a device group
 //                                  (jpge_group_encode_striped: RCCL between distinct
 //                                  devices), e.g. a 16384^2 frame over 8 GPUs;
-//   --restart M                    restart interval in MCUs (DRI/RSTn).
+//   --restart M                    restart interval in MCUs (DRI/RSTn);
+//   --huffman optimal|standard     per-image Huffman tables (the default, the reference's
+//                                  stream) or the ITU T.81 Annex K tables
+//                                  (jpge_set_huffman; not with --gpus / --devices).
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -50,6 +53,7 @@ int main(int argc, char* argv[]) {
     std::vector<int> devs;
     int quality = 50;
     uint32_t restart = 0;
+    int huffman = JPGE_HUFF_OPTIMAL;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-q") && i + 1 < argc) {
             quality = std::atoi(argv[++i]);
@@ -64,6 +68,14 @@ int main(int argc, char* argv[]) {
             while (std::getline(ss, t, ',')) devs.push_back(std::atoi(t.c_str()));
         } else if (!std::strcmp(argv[i], "--restart") && i + 1 < argc) {
             restart = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
+        } else if (!std::strcmp(argv[i], "--huffman") && i + 1 < argc) {
+            const std::string m = argv[++i];
+            if (m == "optimal") huffman = JPGE_HUFF_OPTIMAL;
+            else if (m == "standard") huffman = JPGE_HUFF_STANDARD;
+            else {
+                std::cerr << "jpgenc: --huffman takes optimal or standard" << std::endl;
+                return 1;
+            }
         } else {
             pos.emplace_back(argv[i]);
         }
@@ -74,9 +86,13 @@ int main(int argc, char* argv[]) {
     }
     const std::string jpg = pos.size() < 2 ? "noname.jpg" : pos[1];
     try {
-        if (!devs.empty()) return striped(devs, pos[0], jpg, quality, restart);
+        if (!devs.empty()) {
+            if (huffman != JPGE_HUFF_OPTIMAL) throw std::runtime_error("--huffman standard: not for striped encodes");
+            return striped(devs, pos[0], jpg, quality, restart);
+        }
         auto img = jpge::loadPPM(pos[0]);
         if (restart) jpge::detail::check(jpge_set_restart_interval(jpge::default_context(), restart), "restart");
+        if (huffman) jpge::detail::check(jpge_set_huffman(jpge::default_context(), huffman, nullptr), "huffman");
         img.writeJPEG(jpg, quality);
     } catch (const std::exception& e) {
         std::cerr << "jpgenc: " << e.what() << std::endl;

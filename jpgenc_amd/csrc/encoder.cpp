@@ -356,6 +356,18 @@ struct Encoder::Slot {
     // the lane's wait estimates (histograms when its own thread builds the tables; results)
     WaitGuess* guess_hist = nullptr;
     WaitGuess* guess_result = nullptr;
+    // Fixed Huffman tables: what h_tab and d_tab hold of them (gen 0: nothing; a frame with
+    // per-image tables overwrites both).  A frame whose key equals it finds its code words
+    // and headers on the device already.
+    struct FixedKey {
+        uint64_t gen = 0;  // the setting (Encoder::huff_gen_)
+        uint32_t w = 0, h = 0, restart = 0, samp = 0;  // samp: Y sampling (H << 4 | V), 0 = one component
+        uint8_t qy[64] = {}, qc[64] = {};
+        bool operator==(const FixedKey& o) const {
+            return gen == o.gen && w == o.w && h == o.h && restart == o.restart && samp == o.samp &&
+                   !std::memcmp(qy, o.qy, 64) && !std::memcmp(qc, o.qc, 64);
+        }
+    } fixed;
 
     uint32_t* gate() const { return reinterpret_cast<uint32_t*>(h_result + 6); }
 
@@ -446,6 +458,65 @@ int Encoder::set_subsampling(int mode) {
     uint32_t yh, bpm, cf;
     if (!mode_shape(mode, yh, bpm, cf)) return kErrArg;
     mode_ = mode;
+    return kOk;
+}
+
+int Encoder::set_huffman(int mode, const HuffSpec* specs) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    if (const int st = huff_setting_check(mode, specs)) return st;
+    if (mode) {
+        // the code words once, here: no frame of this setting builds a table
+        const HuffSpec* src = mode == 1 ? kAnnexKHuffman : specs;
+        for (int t = 0; t < 4; ++t) {
+            huff_specs_[t] = src[t];
+            huff_spec_table(huff_specs_[t], huff_tabs_[t]);
+            for (int i = 0; i < 256; ++i)
+                huff_words_[t * 256 + i] = ((uint32_t)huff_tabs_[t].len[i] << 16) | (huff_tabs_[t].code[i] & 0xFFFF);
+        }
+        ++huff_gen_;
+    }
+    huff_mode_ = mode;
+    return kOk;
+}
+
+void Encoder::huffman(int* mode, HuffSpec* specs) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    if (mode) *mode = huff_mode_;
+    if (specs && huff_mode_)
+        for (int t = 0; t < 4; ++t) specs[t] = huff_specs_[t];
+}
+
+// A frame's code words and headers in a fixed mode.  The headers depend on the frame's
+// size, quantisers, sampling and restart interval and on the tables, all known when the
+// frame is queued; a slot that coded such a frame last keeps them, on the host and on the
+// device (a lane's steady state on one geometry writes neither).
+int Encoder::fixed_tables(Slot& s, bool& fresh) {
+    const bool gray = s.g.gray();
+    Slot::FixedKey k;
+    k.gen = huff_gen_;
+    k.w = s.img_w;
+    k.h = s.img_h;
+    k.restart = s.rst.mcus;
+    k.samp = gray ? 0u : (s.g.yh << 4) | s.g.yv();
+    std::memcpy(k.qy, s.qy, 64);
+    std::memcpy(k.qc, s.qc, 64);
+    s.symbols = 0;  // (counted from the histograms, which a fixed mode does not have)
+    fresh = !(k == s.fixed);
+    if (fresh) {
+        s.fixed.gen = 0;
+        std::memcpy(s.h_tab, huff_words_, kTabBytes);
+        // (one component: the chroma tables' slots stay unused, zeroed as build_tables_from leaves them)
+        if (gray) std::memset(s.h_tab + 2 * 256, 0, 2 * 256 * sizeof(uint32_t));
+        const HuffTable* tp[4] = {&huff_tabs_[0], &huff_tabs_[1], &huff_tabs_[2], &huff_tabs_[3]};
+        const std::vector<uint8_t> hdr = gray ? jfif_headers_gray(s.img_w, s.img_h, s.qy, tp, s.rst.mcus)
+                                              : jfif_headers(s.img_w, s.img_h, s.qy, s.qc, tp, s.rst.mcus,
+                                                             (uint8_t)k.samp);
+        if (hdr.size() > kHdrMax) return kErrInternal;
+        std::memcpy(reinterpret_cast<uint8_t*>(s.h_tab) + kTabBytes, hdr.data(), hdr.size());
+        s.hdr_len = hdr.size();
+        s.fixed = k;
+    }
+    if (s.out_cap && s.out_cap < s.hdr_len + 2) return kErrNoSpace;
     return kOk;
 }
 
@@ -852,8 +923,18 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     s.key_y0 = s.key_c0 = s.key_ncb = 0;
     s.img_w = f.width;
     s.img_h = f.height;
+    if (flags & kFlagFixedTables) {
+        // fixed Huffman tables: the frame's own transform kernel carries its code words and
+        // headers to the device, where they are new there
+        bool fresh = false;
+        if (const int st1 = fixed_tables(s, fresh)) return st1;
+        imp = fresh ? &s : nullptr;
+    } else {
+        s.fixed.gen = 0;  // (per-image tables will overwrite the slot's table buffers)
+    }
     a = fdct_args(s, f.maxval, imp);
     st = stats_args(s);
+    st.fixed = (flags & kFlagFixedTables) ? 1u : 0u;
     s.tables_done.store(0, std::memory_order_relaxed);
     s.export_queued.store(0, std::memory_order_relaxed);
     return kOk;
@@ -962,6 +1043,7 @@ int Encoder::build_tables_from(Slot& s, const uint32_t* cnt_all, const uint64_t*
         return (int64_t)t.tv_sec * 1000000000 + t.tv_nsec;
     };
     const int64_t t0 = cpu_prof_ ? thread_ns() : 0;
+    s.fixed.gen = 0;  // (the slot's table buffers get this frame's own tables)
     HuffTable tabs[4];
     int ok[4] = {0, 0, 0, 0};
     // the four tables are independent; the AC tables dominate
@@ -1099,6 +1181,8 @@ int Encoder::finish(Slot& s, FrameDesc& f, uint32_t flags, bool guess_wait, cons
 int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
+    flags &= ~kFlagFixedTables;
+    if (huff_mode_) return encode_fixed(f, qy, qc, flags | kFlagFixedTables);
     Slot& s = *lanes_[0]->slots[0];
     using clk = std::chrono::steady_clock;
     clk::time_point T[6];
@@ -1215,12 +1299,39 @@ int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], ui
     return st;
 }
 
+// A single image with fixed Huffman tables: the tables and the headers are known before
+// the frame, so the four kernels are queued back to back (K1 carrying the code words and
+// headers to the device where the slot does not hold them yet), and the call waits for the
+// pack kernel's result word alone: no gate kernel, no table thread, no histogram wait.
+int Encoder::encode_fixed(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags) {
+    Slot& s = *lanes_[0]->slots[0];
+    int st = phase1(s, f, qy, qc, flags, nullptr, /*export_hist=*/false);
+    if (!st) st = launch_entropy_phase(s, nullptr, /*lone=*/true);
+    if (st) s.fixed.gen = 0;  // (the tables may not have reached the device)
+    if (!st) st = finish(s, f, flags);
+    // (every output byte in place: as encode())
+    const bool await_end = st || !(flags & kFlagDeviceOutput) || lanes_.size() != 1;
+    if (await_end) {
+        if (hipEventRecord(lanes_[0]->done, s.stream) != hipSuccess) {
+            hipStreamSynchronize(s.stream);
+        } else {
+            const hipError_t w = wait_event(lanes_[0]->done);
+            if (w != hipSuccess && !st) st = kErrHip;
+        }
+    }
+    f.status = st;
+    return st;
+}
+
 int Encoder::encode_batch(FrameDesc* fr, int n, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     const auto t_enter = std::chrono::steady_clock::now();
     JPGE_HIP(hipSetDevice(device_));
     for (int i = 0; i < n; ++i) fr[i].status = 0;
     if (n <= 0) return kOk;
+    // (fixed Huffman tables: the lanes run the pipeline without the host in the middle)
+    const bool fixed = huff_mode_ != 0;
+    flags = (flags & ~kFlagFixedTables) | (fixed ? kFlagFixedTables : 0u);
     // Frames are dealt dynamically: a lane takes the batch's next frame (or frame set)
     // when its pipeline has room, so lanes finish together.  Lane 0 runs on the calling
     // thread.
@@ -1230,14 +1341,16 @@ int Encoder::encode_batch(FrameDesc* fr, int n, const uint8_t qy[64], const uint
         if (const int st = add_slots(*lanes_[l], (lookahead_ + drain_lag_ + 1) * set)) return st;
     std::atomic<int> next{0};
     for (int l = 1; l < nl; ++l)
-        lanes_[l]->post([this, l, fr, n, &next, set, qy, qc, flags] {
+        lanes_[l]->post([this, l, fr, n, &next, set, qy, qc, flags, fixed] {
             hipSetDevice(device_);
-            return run_lane(*lanes_[l], fr, n, &next, set, qy, qc, flags);
+            return fixed ? run_lane_fixed(*lanes_[l], fr, n, &next, set, qy, qc, flags)
+                         : run_lane(*lanes_[l], fr, n, &next, set, qy, qc, flags);
         });
     // (napping on the calling thread: ~1 us timer slack for the call, restored after)
     const long slack = nap_ ? prctl(PR_GET_TIMERSLACK, 0, 0, 0, 0) : -1;
     if (slack > 0) prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);
-    int st = run_lane(*lanes_[0], fr, n, &next, set, qy, qc, flags);
+    int st = fixed ? run_lane_fixed(*lanes_[0], fr, n, &next, set, qy, qc, flags)
+                   : run_lane(*lanes_[0], fr, n, &next, set, qy, qc, flags);
     if (slack > 0) prctl(PR_SET_TIMERSLACK, (unsigned long)slack, 0, 0, 0);
     const auto t_lane0 = std::chrono::steady_clock::now();
     for (int l = 1; l < nl; ++l) {
@@ -1536,11 +1649,108 @@ int Encoder::run_lane(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* 
     return first_err;
 }
 
+// A lane's pipeline with fixed Huffman tables.  Nothing of a frame waits on the host: its
+// tables and headers are known when it is queued (fixed_tables), so step i queues K1(i),
+// K2(i) (the instance without histograms) and set i's entropy kernels back to back, and
+// drains set i - D.  There is no histogram export, no table import of another set and no
+// table build; sets, the slot ring, the drain and the result words are run_lane's.
+int Encoder::run_lane_fixed(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* next, int set,
+                            const uint8_t qy[64], const uint8_t qc[64], uint32_t flags) {
+    const int S = (int)ln.slots.size() / set;  // slot sets (add_slots: > drain lag)
+    std::vector<int> mine;  // batch indices of the frames this lane took, in its order
+    mine.reserve(total);
+    auto members = [&](int t) { return std::min(set, (int)mine.size() - t * set); };
+    auto frame = [&](int t, int m) -> FrameDesc& { return frames[mine[t * set + m]]; };
+    auto slot = [&](int t, int m) -> Slot& { return *ln.slots[(t % S) * set + m]; };
+    int first_err = kOk;
+    auto note = [&](int t, int m, int st) {
+        if (st) slot(t, m).fixed.gen = 0;  // (its tables may not have reached the device)
+        if (st && !frame(t, m).status) frame(t, m).status = st;
+        if (st && !first_err) first_err = st;
+    };
+    const int D = drain_lag_;
+    int n = 0;         // sets taken so far
+    bool open = true;  // the batch may still have frames
+    for (int i = 0;; ++i) {
+        if (open && i == n) {  // room for a new set: take the batch's next frames
+            const int g = next->fetch_add(set, std::memory_order_relaxed);
+            if (g < total) {
+                for (int m = 0; m < set && g + m < total; ++m) mine.push_back(g + m);
+                ++n;
+            } else {
+                open = false;
+            }
+        }
+        if (!open && i >= n + D) break;
+        if (i < n) {
+            Slot* ss[kMaxSet];  // the members whose K1 and K2 are queued
+            int ms[kMaxSet], ok = 0;
+            if (set == 1) {
+                Slot& s = slot(i, 0);
+                note(i, 0, phase1(s, frame(i, 0), qy, qc, flags, nullptr, /*export_hist=*/false));
+                if (!frame(i, 0).status) {
+                    ss[0] = &s;
+                    ms[ok++] = 0;
+                }
+            } else {
+                FdctArgs fa[kMaxSet];
+                StatsArgs sa[kMaxSet];
+                for (int m = 0; m < members(i); ++m) {
+                    Slot& s = slot(i, m);
+                    const int st = prep1(s, frame(i, m), qy, qc, flags, nullptr, fa[ok], sa[ok]);
+                    note(i, m, st);
+                    if (st) continue;
+                    ss[ok] = &s;
+                    ms[ok++] = m;
+                }
+                if (ok) {
+                    const int st = phase1_set(ss, ok, fa, sa);
+                    for (int q = 0; q < ok; ++q) note(i, ms[q], st);
+                    if (st) ok = 0;
+                }
+            }
+            // the same set's entropy kernels: one launch per kernel for the set, or frame by
+            // frame (a single frame; a member its code kernel does not place)
+            EntropyArgs ea[kMaxSet];
+            bool as_set = set > 1;
+            Slot* tm = nullptr;  // (a sampled set's member: its events time the launches)
+            for (int q = 0; q < ok; ++q) {
+                ea[q] = entropy_args(*ss[q]);
+                as_set = as_set && ea[q].done;
+                if (ss[q]->timed && !tm) tm = ss[q];
+            }
+            if (ok && as_set) {
+                for (int q = 0; q < ok; ++q) ss[q]->h_result[2] = 0;
+                const KTimer tc{tm ? tm->ev[4] : nullptr, tm ? tm->ev[5] : nullptr};
+                const KTimer tp{tm ? tm->ev[6] : nullptr, tm ? tm->ev[7] : nullptr};
+                const hipError_t e = launch_entropy_set(ea, ok, ss[0]->stream, tm ? &tc : nullptr, tm ? &tp : nullptr);
+                for (int q = 0; q < ok; ++q) note(i, ms[q], e == hipSuccess ? kOk : kErrHip);
+            } else {
+                for (int q = 0; q < ok; ++q) note(i, ms[q], launch_entropy_phase(*ss[q], nullptr));
+            }
+        }
+        const int k = i - D;
+        if (k >= 0 && k < n) {
+            for (int m = 0; m < members(k); ++m) {
+                Slot& s = slot(k, m);
+                if (!frame(k, m).status) note(k, m, finish(s, frame(k, m), flags, /*guess_wait=*/m == 0));
+                else hipStreamSynchronize(s.stream);
+            }
+        }
+    }
+    // every output byte is in place: the stream's tail, awaited by spinning (as run_lane)
+    JPGE_HIP(hipEventRecord(ln.done, ln.stream));
+    JPGE_HIP(wait_event(ln.done));
+    if (cpu_prof_) cpu_frames_.fetch_add((int64_t)mine.size(), std::memory_order_relaxed);
+    return first_err;
+}
+
 int Encoder::fdct_quant(const FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags,
                         int16_t* y, int16_t* cb, int16_t* cr) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = *lanes_[0]->slots[0];
+    flags &= ~kFlagFixedTables;  // (the stage entries are the same in every Huffman mode)
     int st = phase1(s, f, qy, qc, flags | kFlagDeviceOutput | kFlagCoefficients, nullptr, true);
     if (st) { hipStreamSynchronize(s.stream); return st; }
     JPGE_HIP(hipStreamSynchronize(s.stream));
@@ -1568,6 +1778,7 @@ int Encoder::symbol_stats(const FrameDesc& f, const uint8_t qy[64], const uint8_
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = *lanes_[0]->slots[0];
+    flags &= ~kFlagFixedTables;
     int st = phase1(s, f, qy, qc, flags | kFlagDeviceOutput, nullptr, true);
     if (st) { hipStreamSynchronize(s.stream); return st; }
     JPGE_HIP(hipStreamSynchronize(s.stream));
@@ -1591,6 +1802,7 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     JPGE_HIP(hipSetDevice(device_));
     if (!d.rgb || !last_dc || d.width == 0 || d.height == 0 || d.width > 65535 || d.height > 65535) return kErrArg;
     if (mode_ != 420) return kErrArg;  // stripes are S420_m (the reference's subsampling)
+    if (huff_mode_) return kErrArg;    // and share per-image tables (the histogram all-reduce)
     if (fmt_planes(fmt_) != 1 || fmt_gray(fmt_)) return kErrArg;  // and interleaved colour (the stripe pointer is one row of pixels)
     if (d.maxval < 1 || d.maxval > 255) return kErrRange;
     const uint32_t mh_img = (d.height + 15) / 16;
@@ -1636,7 +1848,7 @@ int Encoder::stripe_stats(const int32_t seed[3], uint32_t counts[1024], uint64_t
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = *lanes_[0]->slots[0];
-    if (!s.in_dev || !seed || !counts || !first) return kErrArg;
+    if (!s.in_dev || !seed || !counts || !first || huff_mode_) return kErrArg;
     for (int c = 0; c < 3; ++c) s.seed.v[c] = seed[c];
     const StatsArgs st = stats_args(s);
     JPGE_HIP(launch_stats(st, s.stream));
@@ -1657,7 +1869,7 @@ int Encoder::stripe_code(const uint32_t counts[1024], const uint64_t first[1024]
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = *lanes_[0]->slots[0];
-    if (!s.in_dev || !counts || !first || !sum) return kErrArg;
+    if (!s.in_dev || !counts || !first || !sum || huff_mode_) return kErrArg;
     s.out_dev = nullptr;
     s.out_cap = 0;
     if (const int st = build_tables_from(s, counts, first, true)) return st;
@@ -1724,7 +1936,7 @@ int Encoder::stripe_pack(const StripeSummary* all, int n, int index, uint8_t* ou
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = *lanes_[0]->slots[0];
-    if (!s.in_dev || !out_dev || !s.hdr_len) return kErrArg;
+    if (!s.in_dev || !out_dev || !s.hdr_len || huff_mode_) return kErrArg;
     uint64_t p_ext = 0, q_ext = 0;
     uint32_t head = 0;
     size_t off = 0, total = 0;
@@ -1952,6 +2164,7 @@ int Encoder::encode_planes(const double* const planes[3], uint32_t rows, uint32_
     JPGE_HIP(hipSetDevice(device_));
     for (int c = 0; c < 3; ++c)
         if (!planes[c]) return kErrArg;
+    if (huff_mode_) return kErrArg;  // (writeJPEG's per-image tables only)
     if (!out || !len || !qy || !qc || rows == 0 || cols == 0 || rows % 16 || cols % 16 || rows > 65536 ||
         cols > 65536 || real_w == 0 || real_h == 0 || real_w > 65535 || real_h > 65535)
         return kErrArg;

@@ -25,6 +25,7 @@ namespace jpge {
 constexpr uint32_t kFlagDeviceInput = 1u;
 constexpr uint32_t kFlagDeviceOutput = 2u;
 constexpr uint32_t kFlagCoefficients = 1u << 30;  // (internal) the frame's coefficients are read back
+constexpr uint32_t kFlagFixedTables = 1u << 29;   // (internal) the frame is coded with the context's fixed Huffman tables
 
 struct FrameDesc {
     const uint8_t* rgb = nullptr;
@@ -138,6 +139,15 @@ class Encoder {
         f.plane_stride = plane_stride_;
     }
 
+    // Huffman tables of the following encodes (jpge.h JPGE_HUFF_*): 0 per-image optimal
+    // tables (the reference's stream), 1 ITU T.81 Annex K, 2 the caller's four tables
+    // (Y-DC, Y-AC, C-DC, C-AC; validated: host_io.hpp huff_spec_valid).  In a fixed mode
+    // (1, 2) no frame waits on the host between its statistics and entropy kernels; the
+    // stripe phases and encode_planes refuse it.
+    int set_huffman(int mode, const HuffSpec* specs);
+    // the setting; specs (optional): the four tables of a fixed mode (optimal: untouched)
+    void huffman(int* mode, HuffSpec* specs);
+
     int lanes() const { return (int)lanes_.size(); }
 
   private:
@@ -179,6 +189,17 @@ class Encoder {
     // (frames go in sets of `set` when set > 1: a pipeline step is a set, one launch per kernel)
     int run_lane(Lane& ln, FrameDesc* fr, int total, std::atomic<int>* next, int set, const uint8_t qy[64],
                  const uint8_t qc[64], uint32_t flags);
+    // ---- fixed Huffman tables (set_huffman) ----
+    // encode()'s single image: K1, K2, the code and the pack kernel queued at once
+    int encode_fixed(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags);
+    // run_lane's pipeline without the host in the middle: a step queues K1, K2 and the
+    // entropy kernels of the same set
+    int run_lane_fixed(Lane& ln, FrameDesc* fr, int total, std::atomic<int>* next, int set, const uint8_t qy[64],
+                       const uint8_t qc[64], uint32_t flags);
+    // the fixed tables' code words and the frame's headers into the slot's staging buffer,
+    // unless the slot's buffers (host and device) hold them already; fresh: they are new in
+    // h_tab, and the frame's transform kernel has to carry them to the device
+    int fixed_tables(Slot& s, bool& fresh);
 
     int device_ = 0;
     int timing_every_ = 0;
@@ -199,6 +220,14 @@ class Encoder {
     uint32_t restart_mcus_ = 0; // restart interval (jpge_set_restart_interval)
     int mode_ = 420;            // subsampling mode (jpge_set_subsampling)
     int fmt_ = kFmtRgb8;        // input layout (jpge_set_input_format)
+    // Huffman mode (jpge_set_huffman) and, in a fixed mode, the four tables: as given, as
+    // codes, and as the [4][256] (len << 16) | code words the code kernel reads (built once,
+    // at set_huffman); the generation numbers a setting (a slot remembers whose tables it holds)
+    int huff_mode_ = 0;
+    HuffSpec huff_specs_[4] = {};
+    HuffTable huff_tabs_[4];
+    uint32_t huff_words_[4 * 256] = {};
+    uint64_t huff_gen_ = 0;
     size_t plane_stride_ = 0;
     // entropy workgroups: the override, else 512 for a single lane's lone frames (their
     // latency: -5 us at 4K) and seg_layout's default (384, or 2 tiles per workgroup under

@@ -285,6 +285,11 @@ int jpge_group_encode_striped(jpge_group* g, const uint8_t* rgb, uint32_t width,
         int fmt = JPGE_FMT_RGB8;
         if (const int st = jpge_get_input_format(c, &fmt, nullptr)) return st;
         if (fmt != JPGE_FMT_RGB8) return (int)JPGE_E_ARG;
+        // and shares one image's tables over the stripes (the histogram all-reduce): the
+        // per-image mode only
+        int huff = JPGE_HUFF_OPTIMAL;
+        if (const int st = jpge_get_huffman(c, &huff, nullptr)) return st;
+        if (huff != JPGE_HUFF_OPTIMAL) return (int)JPGE_E_ARG;
     }
     const size_t row = (size_t)width * 3, pitch = stride ? stride : row;
     if (pitch < row) return (int)JPGE_E_ARG;

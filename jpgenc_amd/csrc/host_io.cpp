@@ -249,6 +249,88 @@ std::vector<uint8_t> jfif_headers_gray(uint32_t rw, uint32_t rh, const uint8_t q
     return o;
 }
 
+// ITU T.81 Annex K, tables K.3, K.5, K.4, K.6 (BITS and HUFFVAL as the standard lists them).
+const HuffSpec kAnnexKHuffman[4] = {
+    {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
+     {0x00, 0x01, 0x02, 0x03, 0x04, 0x05, 0x06, 0x07, 0x08, 0x09, 0x0A, 0x0B}},
+    {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125},
+     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07,
+      0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xA1, 0x08, 0x23, 0x42, 0xB1, 0xC1, 0x15, 0x52, 0xD1, 0xF0,
+      0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18, 0x19, 0x1A, 0x25, 0x26, 0x27, 0x28,
+      0x29, 0x2A, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49,
+      0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+      0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+      0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7,
+      0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5,
+      0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2,
+      0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8,
+      0xF9, 0xFA}},
+    {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0},
+     {0x00, 0x01, 0x02, 0x03, 0x04, 0x05, 0x06, 0x07, 0x08, 0x09, 0x0A, 0x0B}},
+    {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119},
+     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71,
+      0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xA1, 0xB1, 0xC1, 0x09, 0x23, 0x33, 0x52, 0xF0,
+      0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25, 0xF1, 0x17, 0x18, 0x19, 0x1A, 0x26,
+      0x27, 0x28, 0x29, 0x2A, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+      0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68,
+      0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
+      0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5,
+      0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3,
+      0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA,
+      0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8,
+      0xF9, 0xFA}},
+};
+
+bool huff_spec_valid(const HuffSpec& spec, bool ac) {
+    uint32_t n = 0, kraft = 0;
+    for (int l = 1; l <= 16; ++l) {
+        n += spec.bits[l - 1];
+        kraft += (uint32_t)spec.bits[l - 1] << (16 - l);
+    }
+    if (n > 256 || kraft >= (1u << 16)) return false;
+    bool have[256] = {};
+    for (uint32_t i = 0; i < n; ++i) {
+        if (have[spec.huffval[i]]) return false;
+        have[spec.huffval[i]] = true;
+    }
+    if (!ac) {
+        for (int c = 0; c <= 11; ++c)
+            if (!have[c]) return false;
+        return true;
+    }
+    if (!have[0x00] || !have[0xF0]) return false;
+    for (int run = 0; run < 16; ++run)
+        for (int size = 1; size <= 10; ++size)
+            if (!have[(run << 4) | size]) return false;
+    return true;
+}
+
+int huff_setting_check(int mode, const HuffSpec* specs) {
+    if (mode < 0 || mode > 2) return kErrArg;
+    if (mode != 2) return kOk;  // (specs are read for the caller's tables only)
+    if (!specs) return kErrArg;
+    for (int t = 0; t < 4; ++t)
+        if (!huff_spec_valid(specs[t], (t & 1) != 0)) return kErrArg;
+    return kOk;
+}
+
+void huff_spec_table(const HuffSpec& spec, HuffTable& out) {
+    out = HuffTable();
+    uint32_t code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        out.bits[l] = spec.bits[l - 1];
+        for (int i = 0; i < spec.bits[l - 1] && k < 256; ++i, ++k) {
+            const uint8_t s = spec.huffval[k];
+            out.huffval[k] = s;
+            out.code[s] = code++;
+            out.len[s] = (uint8_t)l;
+        }
+        code <<= 1;
+    }
+    out.nsym = k;
+}
+
 namespace {
 int synth_threads(uint32_t h) {  // test-data synthesis: a few threads for large frames
     const unsigned hw = std::thread::hardware_concurrency();

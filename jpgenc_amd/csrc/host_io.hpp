@@ -65,6 +65,28 @@ std::vector<uint8_t> jfif_headers(uint32_t real_width, uint32_t real_height, con
 std::vector<uint8_t> jfif_headers_gray(uint32_t real_width, uint32_t real_height, const uint8_t qy[64],
                                        const HuffTable* const tables[2], uint32_t restart_mcus = 0);
 
+// ---- fixed Huffman tables (jpge_set_huffman; an addition, nothing in the reference) ----
+// A table in DHT form, as jpge_huff_spec: bits[l - 1] codes of length l, then the symbols.
+struct HuffSpec {
+    uint8_t bits[16];
+    uint8_t huffval[256];
+};
+// ITU T.81 Annex K tables K.3 (luminance DC), K.5 (luminance AC), K.4 (chrominance DC) and
+// K.6 (chrominance AC), in the library's table order Y-DC, Y-AC, C-DC, C-AC.
+extern const HuffSpec kAnnexKHuffman[4];
+// A table the encoder may code any 8-bit baseline frame with, without looking at the frame:
+// at most 256 symbols, none twice, Kraft sum (sum of bits[l-1] * 2^(16-l)) below 2^16 (so no
+// code is all ones, T.81 C.2), and complete: a DC table (ac = false) holds categories
+// 0..11, an AC table 0x00, 0xF0 and every run 0..15 x size 1..10.
+bool huff_spec_valid(const HuffSpec& spec, bool ac);
+// jpge_set_huffman's argument check: kOk, or kErrArg for an unknown mode, mode 2 (the
+// caller's tables) without specs, or a spec of it that is not valid (specs 1 and 3 are AC).
+int huff_setting_check(int mode, const HuffSpec* specs);
+// Canonical codes (T.81 Annex C, figures C.1-C.3) of a valid spec: codes of one length
+// count up in huffval order, and the first code of a length is the last one of the shorter
+// length, plus one, shifted left.
+void huff_spec_table(const HuffSpec& spec, HuffTable& out);
+
 // Deterministic synthetic RGB8 frame (integer-only, identical on every host):
 // kind 0 = smooth gradients + texture + noise (photo-like), 1 = uniform random
 // bytes (worst-case symbol statistics), 2 = flat colour.

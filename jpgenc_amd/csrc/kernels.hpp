@@ -228,6 +228,10 @@ struct StatsArgs {
     uint16_t* recs;      // [tiles][kTileRecords] symbol records
     uint32_t* tcount;    // [tiles][kRecSub] records per sub-stream
     uint32_t wgs = 0;    // workgroup count (0 = 3 per CU; the pipeline passes its own, stats_grid)
+    // 1: fixed Huffman tables (jpge_set_huffman): the instance without histograms, which
+    // reads none of hist, key_*, done, host_* and seq (in the padding after wgs: the
+    // argument block's layout is unchanged)
+    uint32_t fixed = 0;
     uint64_t* dbg;
     // Set (single frames): the last workgroup to finish exports the histograms into
     // mapped host memory (export_hist), in place of a hist_export_kernel launch.  `done`

@@ -8,6 +8,8 @@
 // global replicas.  First-occurrence keys (text index of the symbol, huffman.hpp)
 // are kept workgroup-relative in u32 LDS words and widened at the flush; the global
 // key is stored inverted so atomicMax keeps the minimum.
+// With fixed Huffman tables (jpge_set_huffman) nobody reads the histograms: the kHist =
+// false instances write the records alone and have no counters, keys, flush or export.
 #include <algorithm>
 #include <cstddef>
 #include <type_traits>
@@ -79,16 +81,27 @@ struct K2WLds {
     uint32_t sb0[kWMaxSubs + 1];                         // the workgroup's sub-streams' first blocks, and the end
     uint32_t next;                                       // the next sub-stream to take
 };
+// The fixed-table instance's (kHist = false): no counters and no keys
+struct K2WLdsFixed {
+    alignas(16) uint32_t stage[kWWaves][8 * 32 + 32];
+    uint32_t sb0[kWMaxSubs + 1];
+    uint32_t next;
+};
 
 // kGray: the one-component instance (Geometry::gray(): an MCU is one block, no chroma; the
 // chain, the text and the keys run in block order).  The three-component instance is the
 // code it was before that instance existed.
-template <int kN, bool kGray>
+// kHist = false: the fixed-table instance (jpge_set_huffman: the tables are known before
+// the frame, so nobody needs its histograms).  It writes the same records and tcount and
+// has none of the histogram machinery: no LDS counters, first-occurrence keys, key bases,
+// flush or export; a.hist, a.key_*, a.done and a.host_* are not read.  The kHist = true
+// instances are the code they were before this one existed.
+template <int kN, bool kGray, bool kHist = true>
 __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe))) void stats_wave_kernel(FrameSet<StatsArgs, kN> fs) {
     const uint32_t set_f = (kN == 1 ? 0u : set_member_rolled(fs.wg0, fs.n, blockIdx.x));  // (frame sets: kernels.hpp)
     const StatsArgs& a = fs.a[set_f];
     const uint32_t bid = blockIdx.x - fs.wg0[set_f], nbk = fs.wg0[set_f + 1] - fs.wg0[set_f];
-    __shared__ K2WLds L;
+    __shared__ std::conditional_t<kHist, K2WLds, K2WLdsFixed> L;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -129,10 +142,12 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
         load_dcs_at((uint32_t)b, n);
     }
     static_assert((kWCopies * kWCopyWords) % 4 == 0 && kWKeyWords % 4 == 0, "16-byte initialisation");
-    for (int i = tid; i < (int)(kWCopies * kWCopyWords / 4); i += kWThreads)
-        reinterpret_cast<uint4*>(L.cnt)[i] = make_uint4(0, 0, 0, 0);
-    for (int i = tid; i < (int)(kWKeyWords / 4); i += kWThreads)
-        reinterpret_cast<uint4*>(L.key)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if constexpr (kHist) {
+        for (int i = tid; i < (int)(kWCopies * kWCopyWords / 4); i += kWThreads)
+            reinterpret_cast<uint4*>(L.cnt)[i] = make_uint4(0, 0, 0, 0);
+        for (int i = tid; i < (int)(kWKeyWords / 4); i += kWThreads)
+            reinterpret_cast<uint4*>(L.key)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
     for (uint32_t i = tid; i <= ns; i += kWThreads) {  // their first blocks (block numbers < 2^32: launch_stats)
         uint64_t b;
         uint32_t n;
@@ -145,14 +160,16 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
     // workgroup counts itself once its flush atomics (device-coherent) have completed;
     // the one completing the count reads every workgroup's counts and keys
     auto export_if_last = [&]() {
-        if (!a.done) return;
-        vm_drain();
-        __syncthreads();
-        if (tid == 0) L.next = atomicAdd(a.done, 1u) == nbk - 1 ? 1u : 0u;
-        __syncthreads();
-        if (L.next) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            export_hist<kWThreads>(a.hist, a.host_cnt, a.host_key, a.host_seq, a.seq, tid);
+        if constexpr (kHist) {
+            if (!a.done) return;
+            vm_drain();
+            __syncthreads();
+            if (tid == 0) L.next = atomicAdd(a.done, 1u) == nbk - 1 ? 1u : 0u;
+            __syncthreads();
+            if (L.next) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                export_hist<kWThreads>(a.hist, a.host_cnt, a.host_key, a.host_seq, a.seq, tid);
+            }
         }
     };
     if (ns == 0) {
@@ -160,14 +177,16 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
         return;
     }
     // key bases (keys are kept relative to them): the workgroup's first MCU row
-    const uint32_t mrow0 = __builtin_amdgcn_readfirstlane((L.sb0[0] / bpm) / mw);
+    // (the fixed-table instance keeps no keys: no bases)
+    const uint32_t mrow0 = kHist ? __builtin_amdgcn_readfirstlane((L.sb0[0] / bpm) / mw) : 0u;
     const uint32_t ybase = mrow0 * yv * ybw, cbase = mrow0 * mw;
     JPGE_STAMP(0);
     uint64_t tq = JPGE_NOW();
 
     const uint32_t natoff = kZzToNat[lane];  // this lane's coefficient in a staged block (int16 index)
     const uint32_t k2p = 2u * (uint32_t)lane;
-    uint32_t* const cnt = L.cnt + (uint32_t)(lane & (kWCopies - 1)) * kWCopyWords;
+    uint32_t* cnt = nullptr;
+    if constexpr (kHist) cnt = L.cnt + (uint32_t)(lane & (kWCopies - 1)) * kWCopyWords;
     const uint32_t shl = (uint32_t)(64 - lane) & 63u;
     const uint64_t lanes_ac = ~1ull;  // every lane but the DC
     const uint32_t dc_tab = lane == 0 ? 1u << 14 : 0u;  // (a record's table bits: 2t + 1 -> 2t)
@@ -197,8 +216,10 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
         const uint32_t mrow = m6 / mw, mcol = m6 - mrow * mw;
         const int comp = kGray ? 0 : ((int)k < (int)bpm - 2 ? 0 : (int)k - ((int)bpm - 3));  // (block_comp)
         // text index (the Y text in block raster order; all Cr after all Cb), relative to the bases
-        const uint32_t rel = comp == 0 ? (mrow * yv + (k >> yhs)) * ybw + mcol * yh + (k & (yh - 1)) - ybase
-                                       : (m6 - cbase) | (comp == 2 ? 0x80000000u : 0u);
+        // (the fixed-table instance: a block's word is its table select alone)
+        const uint32_t rel = !kHist      ? 0u
+                             : comp == 0 ? (mrow * yv + (k >> yhs)) * ybw + mcol * yh + (k & (yh - 1)) - ybase
+                                         : (m6 - cbase) | (comp == 2 ? 0x80000000u : 0u);
         const uint32_t tsel = comp != 0;
         // the block loop reads one word per block: the AC key base, text index * 128 + d,
         // whose low bit d is the table select (a key is base + 2p: keys are compared only
@@ -310,10 +331,12 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
                 if (nzr) {
                     const uint16_t zrec = (uint16_t)(b.Tj | (15u << 10));
                     for (uint32_t z = 1; z <= nzr; ++z) srec[base + b.rk - z] = zrec;
-                    const uint32_t wz = b.acw + kRunStride * 15u;  // (symbol 0xF0)
-                    atomicAdd(&cnt[wz], nzr);
-                    const uint32_t kz = b.acbj + k2p - 1u;
-                    if (kz < L.key[wz]) atomicMin(&L.key[wz], kz);
+                    if constexpr (kHist) {
+                        const uint32_t wz = b.acw + kRunStride * 15u;  // (symbol 0xF0)
+                        atomicAdd(&cnt[wz], nzr);
+                        const uint32_t kz = b.acbj + k2p - 1u;
+                        if (kz < L.key[wz]) atomicMin(&L.key[wz], kz);
+                    }
                 }
             }
             if (__builtin_amdgcn_inverse_ballot_w64(b.em)) {
@@ -322,9 +345,11 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
                     const uint32_t cat = (uint32_t)__builtin_amdgcn_frexp_expf((float)c), sh = cat - kRecXBits;
                     srec[base + b.rk + 1] = (uint16_t)(b.Tj | (sh << 10) | (extra_bits(c, (int)cat) & ((1u << sh) - 1u)));
                 }
-                atomicAdd(&cnt[b.w], 1u);
-                const uint32_t kk = b.acbj + k2p;
-                if (kk < L.key[b.w]) atomicMin(&L.key[b.w], kk);
+                if constexpr (kHist) {
+                    atomicAdd(&cnt[b.w], 1u);
+                    const uint32_t kk = b.acbj + k2p;
+                    if (kk < L.key[b.w]) atomicMin(&L.key[b.w], kk);
+                }
             }
             return (uint32_t)__builtin_popcountll(b.em) + zt + (uint32_t)__builtin_popcountll(b.bg);  // DC, non-zeros, EOB, ZRLs, continuations
         };
@@ -362,19 +387,21 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
                     const bool ia = __builtin_amdgcn_inverse_ballot_w64(A.em), ib = __builtin_amdgcn_inverse_ballot_w64(B.em);
                     __builtin_amdgcn_raw_buffer_store_b16((uint16_t)recA, rrs, ia ? (base + rkA) * 2u : 0x80000000u, 0, 0);
                     __builtin_amdgcn_raw_buffer_store_b16((uint16_t)recB, rrs, ib ? (baseB + rkB) * 2u : 0x80000000u, 0, 0);
-                    if (ia) atomicAdd(&cnt[A.w], 1u);
-                    if (ib) atomicAdd(&cnt[B.w], 1u);
-                    // (every lane reads its word: a lane without a record has c = 0, so its
-                    // word is its table's first, and lane 0's is in range too)
-                    const uint32_t kvA = L.key[A.w], kvB = L.key[B.w];
-                    const uint32_t kkA = A.acbj + k2p, kkB = B.acbj + k2p;
-                    // (rare: a first occurrence in this workgroup so far; the masks of the
-                    // compares, which a bool's ballot would rebuild lane by lane)
-                    const uint64_t fA = A.em & __builtin_amdgcn_ballot_w64(kkA < kvA);
-                    const uint64_t fB = B.em & __builtin_amdgcn_ballot_w64(kkB < kvB);
-                    if (fA | fB) {
-                        if (__builtin_amdgcn_inverse_ballot_w64(fA)) atomicMin(&L.key[A.w], kkA);
-                        if (__builtin_amdgcn_inverse_ballot_w64(fB)) atomicMin(&L.key[B.w], kkB);
+                    if constexpr (kHist) {
+                        if (ia) atomicAdd(&cnt[A.w], 1u);
+                        if (ib) atomicAdd(&cnt[B.w], 1u);
+                        // (every lane reads its word: a lane without a record has c = 0, so its
+                        // word is its table's first, and lane 0's is in range too)
+                        const uint32_t kvA = L.key[A.w], kvB = L.key[B.w];
+                        const uint32_t kkA = A.acbj + k2p, kkB = B.acbj + k2p;
+                        // (rare: a first occurrence in this workgroup so far; the masks of the
+                        // compares, which a bool's ballot would rebuild lane by lane)
+                        const uint64_t fA = A.em & __builtin_amdgcn_ballot_w64(kkA < kvA);
+                        const uint64_t fB = B.em & __builtin_amdgcn_ballot_w64(kkB < kvB);
+                        if (fA | fB) {
+                            if (__builtin_amdgcn_inverse_ballot_w64(fA)) atomicMin(&L.key[A.w], kkA);
+                            if (__builtin_amdgcn_inverse_ballot_w64(fB)) atomicMin(&L.key[B.w], kkB);
+                        }
                     }
                     base = baseB + nB;
                 } else {  // (a ZRL block: both again from the stage, exactly)
@@ -393,35 +420,38 @@ __global__ __launch_bounds__(kWThreads) __attribute__((amdgpu_waves_per_eu(kWWpe
         JPGE_ACC(3, tq);
     }
     JPGE_STAMP(2);
-    __syncthreads();
+    // (the fixed-table instance has nothing to flush: the records and their counts are its output)
+    if constexpr (kHist) {
+        __syncthreads();
 
-    const int rep = bid % kHistReplicas;
-    const uint64_t ncb = a.key_ncb ? a.key_ncb : a.g.nmcu();  // Cb blocks of the whole image
-    // (a thread's two words; the global key's atomicMax unconditional: reading the key
-    // first to skip needless atomics held every workgroup one global round trip longer,
-    // K2 alone 68.6 -> 62.6 us per set of 4 4K frames without it)
-    static_assert(1024 == 2 * kWThreads, "two flush words per thread");
-    unsigned long long* gk = reinterpret_cast<unsigned long long*>(a.hist.key);
+        const int rep = bid % kHistReplicas;
+        const uint64_t ncb = a.key_ncb ? a.key_ncb : a.g.nmcu();  // Cb blocks of the whole image
+        // (a thread's two words; the global key's atomicMax unconditional: reading the key
+        // first to skip needless atomics held every workgroup one global round trip longer,
+        // K2 alone 68.6 -> 62.6 us per set of 4 4K frames without it)
+        static_assert(1024 == 2 * kWThreads, "two flush words per thread");
+        unsigned long long* gk = reinterpret_cast<unsigned long long*>(a.hist.key);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const uint32_t i = (uint32_t)tid + (uint32_t)j * kWThreads;
-        const uint32_t t = i >> 8, sy = i & 255u;
-        if (!(t & 1) && sy >= 16) continue;  // (DC tables: categories < 16)
-        const uint32_t w = tab_base(t) + (sy & 15u) + kRunStride * (sy >> 4);
-        uint32_t c = 0;
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t i = (uint32_t)tid + (uint32_t)j * kWThreads;
+            const uint32_t t = i >> 8, sy = i & 255u;
+            if (!(t & 1) && sy >= 16) continue;  // (DC tables: categories < 16)
+            const uint32_t w = tab_base(t) + (sy & 15u) + kRunStride * (sy >> 4);
+            uint32_t c = 0;
 #pragma unroll
-        for (int cp = 0; cp < kWCopies; ++cp) c += L.cnt[cp * kWCopyWords + w];
-        if (!c) continue;
-        atomicAdd(&a.hist.cnt[rep * 1024 + i], c);
-        const uint32_t k32 = L.key[w];
-        uint64_t kb;  // (global texts: a stripe's bases are offset into the whole image)
-        if (t < 2) kb = a.key_y0 + ybase;
-        else kb = a.key_c0 + cbase + ((k32 & 0x80000000u) ? ncb : 0ull);
-        // (AC keys: text index * 128 + 2p + delta + d; DC keys were kept as text index * 128 + d)
-        const uint64_t gkey = (t & 1) ? kb * 128ull + (k32 & 0x7FFFFFFFu) : kb + ((k32 & 0x7FFFFFFFu) >> 7);
-        atomicMax(&gk[i], (unsigned long long)~gkey);
+            for (int cp = 0; cp < kWCopies; ++cp) c += L.cnt[cp * kWCopyWords + w];
+            if (!c) continue;
+            atomicAdd(&a.hist.cnt[rep * 1024 + i], c);
+            const uint32_t k32 = L.key[w];
+            uint64_t kb;  // (global texts: a stripe's bases are offset into the whole image)
+            if (t < 2) kb = a.key_y0 + ybase;
+            else kb = a.key_c0 + cbase + ((k32 & 0x80000000u) ? ncb : 0ull);
+            // (AC keys: text index * 128 + 2p + delta + d; DC keys were kept as text index * 128 + d)
+            const uint64_t gkey = (t & 1) ? kb * 128ull + (k32 & 0x7FFFFFFFu) : kb + ((k32 & 0x7FFFFFFFu) >> 7);
+            atomicMax(&gk[i], (unsigned long long)~gkey);
+        }
+        export_if_last();
     }
-    export_if_last();
     JPGE_STAMP(3);
 }
 
@@ -463,6 +493,13 @@ static hipError_t launch_stats_fs(const FrameSet<StatsArgs, kN>& fs, hipStream_t
         if (fs.wg0[f + 1] - fs.wg0[f] != stats_grid(fs.a[f].seg, fs.a[f].wgs)) return hipErrorInvalidValue;
         // (a set's members share a kernel instance; one component: bpm = 1 goes with yh = 1)
         if (fs.a[f].g.gray() != fs.a[0].g.gray() || (fs.a[f].g.gray() && fs.a[f].g.yh != 1)) return hipErrorInvalidValue;
+    }
+    for (uint32_t f = 1; f < fs.n; ++f)
+        if ((fs.a[f].fixed != 0) != (fs.a[0].fixed != 0)) return hipErrorInvalidValue;
+    if (fs.a[0].fixed) {  // (fixed Huffman tables: no histograms)
+        if (fs.a[0].g.gray())
+            return launch_timed(t, stats_wave_kernel<kN, true, false>, dim3(fs.wg0[fs.n]), dim3(kWThreads), s, fs);
+        return launch_timed(t, stats_wave_kernel<kN, false, false>, dim3(fs.wg0[fs.n]), dim3(kWThreads), s, fs);
     }
     if (fs.a[0].g.gray())
         return launch_timed(t, stats_wave_kernel<kN, true>, dim3(fs.wg0[fs.n]), dim3(kWThreads), s, fs);

@@ -26,8 +26,9 @@ HUFF_TEST   := tests/cpp/bin/test_huffman_fast
 QUANT_TEST  := tests/cpp/bin/test_quant_fast
 EXIT_TEST   := tests/cpp/bin/test_exit_close
 HUFFSPEC_TEST := tests/cpp/bin/test_huffspec
+YUVXF_TEST  := tests/cpp/bin/test_yuvxf
 
-all: $(LIBDIR)/libjpge.so $(BINDIR)/jpgenc $(FACADE_TEST) $(HUFF_TEST) $(QUANT_TEST) $(EXIT_TEST) $(HUFFSPEC_TEST) oracle
+all: $(LIBDIR)/libjpge.so $(BINDIR)/jpgenc $(FACADE_TEST) $(HUFF_TEST) $(QUANT_TEST) $(EXIT_TEST) $(HUFFSPEC_TEST) $(YUVXF_TEST) oracle
 
 # (fdct_*.hip: fdct.hip built per input load shape)
 K1_SHAPES := fdct_bgr8.o fdct_x4.o fdct_planar.o fdct_nv12.o fdct_i420.o fdct_yuv444.o fdct_gray.o
@@ -100,6 +101,12 @@ $(HUFFSPEC_TEST): tests/cpp/test_huffspec.cpp $(SRC)/host_io.cpp $(SRC)/host_io.
 	@mkdir -p tests/cpp/bin
 	$(CXX) $(CXXFLAGS) -o $@ $< $(SRC)/host_io.cpp
 
+# the sample transform of Y, Cb, Cr input: the setting's validation and the presets, host only
+# (tests/test_yuvxf_cpu.py runs it)
+$(YUVXF_TEST): tests/cpp/test_yuvxf.cpp $(SRC)/host_io.cpp $(SRC)/host_io.hpp $(SRC)/huffman.hpp $(SRC)/host_par.hpp
+	@mkdir -p tests/cpp/bin
+	$(CXX) $(CXXFLAGS) -o $@ $< $(SRC)/host_io.cpp
+
 # Host code under AddressSanitizer + UndefinedBehaviorSanitizer (run by
 # tests/test_asan.py in the CPU suite): every host .cpp of the library rebuilt
 # sanitized and linked with the (unsanitized) HIP device objects, plus the host
@@ -109,7 +116,7 @@ ASAN_DIR   := build/asan
 ASAN_BIN   := tests/cpp/bin/asan
 ASAN_OBJS  := $(addprefix $(ASAN_DIR)/,$(HOST_SRCS:.cpp=.o))
 ASAN_TESTS := $(ASAN_BIN)/test_host_asan $(ASAN_BIN)/test_facade $(ASAN_BIN)/test_huffman_fast $(ASAN_BIN)/test_quant_fast \
-              $(ASAN_BIN)/test_huffspec
+              $(ASAN_BIN)/test_huffspec $(ASAN_BIN)/test_yuvxf
 
 $(ASAN_DIR)/%.o: $(SRC)/%.cpp $(HEADERS)
 	@mkdir -p $(ASAN_DIR)
@@ -132,6 +139,10 @@ $(ASAN_BIN)/test_quant_fast: tests/cpp/test_quant_fast.cpp $(SRC)/constants.hpp
 	$(CXX) -std=c++17 -ffp-contract=off -I$(SRC) $(ASAN_FLAGS) -o $@ $<
 
 $(ASAN_BIN)/test_huffspec: tests/cpp/test_huffspec.cpp $(SRC)/host_io.cpp $(SRC)/host_io.hpp $(SRC)/huffman.hpp $(SRC)/host_par.hpp
+	@mkdir -p $(ASAN_BIN)
+	$(CXX) $(CXXFLAGS) $(ASAN_FLAGS) -o $@ $< $(SRC)/host_io.cpp
+
+$(ASAN_BIN)/test_yuvxf: tests/cpp/test_yuvxf.cpp $(SRC)/host_io.cpp $(SRC)/host_io.hpp $(SRC)/huffman.hpp $(SRC)/host_par.hpp
 	@mkdir -p $(ASAN_BIN)
 	$(CXX) $(CXXFLAGS) $(ASAN_FLAGS) -o $@ $< $(SRC)/host_io.cpp
 

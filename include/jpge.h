@@ -228,6 +228,50 @@ int jpge_get_huffman(jpge_ctx* ctx, int* mode, jpge_huff_spec specs[4]);
  * (An addition; replaces nothing in the reference.) */
 int jpge_standard_huffman(int table /*0..3*/, jpge_huff_spec* spec);
 
+/* ---- Sample transform of Y, Cb, Cr input (an addition; replaces nothing in the reference) ----
+ * A JFIF file holds full-range BT.601 samples, and by default a Y, Cb, Cr frame is taken
+ * to hold exactly those.  A video decoder's output is usually studio swing (Y 16..235,
+ * Cb and Cr 16..240) and, above SD, BT.709: the presets below convert such samples to
+ * full-range BT.601 inside the transform kernel, in fp64 with no intermediate rounding to
+ * 8 bits and no pass over the frame.  (All additions.) */
+#define JPGE_YUV_FULL_601     0  /* the default: a sample v is v - 128 (today's stream) */
+#define JPGE_YUV_LIMITED_601  1  /* studio swing, BT.601 matrix: range expansion only   */
+#define JPGE_YUV_LIMITED_709  2  /* studio swing, BT.709 matrix -> full-range BT.601    */
+#define JPGE_YUV_FULL_709     3  /* full range, BT.709 matrix -> full-range BT.601      */
+#define JPGE_YUV_CUSTOM       4  /* the caller's coefficients                           */
+/* With bytes (y, cb, cr) of one pixel (NV12, I420: cb, cr of the pixel's 2x2 cell),
+ * yc = (double)y - y_off, u = (double)cb - 128, v = (double)cr - 128 (all exact), the fp64
+ * planes that enter the pipeline (the reference Image's planes after convertToColorSpace) are
+ *   Y'  = min(max((m[0]*yc + m[1]*u) + m[2]*v, 0), 255) - 128
+ *   Cb' = min(max( m[3]*u + m[4]*v, -128), 127)
+ *   Cr' = min(max( m[5]*u + m[6]*v, -128), 127)
+ * each product and each sum rounded to fp64 on its own, in the order of the brackets (no
+ * fused multiply-add): these rules define the output bytes.  The clamps keep every sample in
+ * the interval of an 8-bit one whatever the input (super-white and out-of-gamut samples
+ * are legal in video), so the coefficient bounds the fixed Huffman tables rest on hold.
+ * (An addition.) */
+typedef struct { double y_off; double m[7]; } jpge_yuv_transform;
+/* The transform of the context's following jpge_encode_rgb8, jpge_encode_batch,
+ * jpge_fdct_quant and jpge_symbol_stats calls on frames in JPGE_FMT_NV12, _I420,
+ * _YUV444_PLANAR (transform per pixel, then the subsampling mode's filter) and _GRAY8 (y_off
+ * and m[0] only: a video's Y plane as a grayscale file); also on a group member's context
+ * (jpge_group_context), and so for jpge_group_encode_batch.  The RGB layouts ignore it.
+ * custom is read for JPGE_YUV_CUSTOM only.  JPGE_E_ARG for an unknown preset, CUSTOM with
+ * custom == NULL, a non-finite value, y_off outside 0..255 or an |m[i]| above 4; the
+ * setting is then unchanged.  Orthogonal to the subsampling mode, the restart interval,
+ * the Huffman mode, lanes and frame sets; the header bytes do not depend on it; maxval must
+ * still be 255, and every refusal of the layouts stands.  JPGE_YUV_FULL_601 runs the same
+ * kernels as a context that never called this.  (An addition.) */
+int jpge_set_yuv_transform(jpge_ctx* ctx, int preset, const jpge_yuv_transform* custom);
+/* The current preset and its coefficients (t may be NULL).  (An addition.) */
+int jpge_get_yuv_transform(jpge_ctx* ctx, int* preset, jpge_yuv_transform* t);
+/* A preset's coefficients; host only, no context.  LIMITED_*: y_off 16, m[0] = 255/219,
+ * the chroma entries scaled by 255/224; *_709: the matrix A601 . inverse(A709) of the
+ * BT.601 (0.299, 0.587, 0.114) and BT.709 (0.2126, 0.7152, 0.0722) luma weights;
+ * JPGE_YUV_FULL_601: the identity (y_off 0, m[0] = m[3] = m[6] = 1).  JPGE_E_ARG for
+ * JPGE_YUV_CUSTOM and unknown presets.  (An addition.) */
+int jpge_yuv_preset(int preset, jpge_yuv_transform* t);
+
 /* Worst-case .jpg size for a frame, in any subsampling mode (header + 2x
  * worst-case entropy + RST markers + EOI). */
 size_t jpge_max_jpeg_bytes(uint32_t width, uint32_t height);

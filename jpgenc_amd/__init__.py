@@ -38,6 +38,11 @@ JPGE_FMT_GRAY8 = 8
 #: the ITU T.81 Annex K tables, or the caller's four tables
 JPGE_HUFF_OPTIMAL, JPGE_HUFF_STANDARD, JPGE_HUFF_CUSTOM = 0, 1, 2
 
+#: sample transforms of Y, Cb, Cr and gray input (jpge.h JPGE_YUV_*): full-range BT.601 (JFIF's
+#: own samples, the default), studio swing with the BT.601 or the BT.709 matrix, full-range
+#: BT.709, or the caller's coefficients; converted inside the transform kernel
+JPGE_YUV_FULL_601, JPGE_YUV_LIMITED_601, JPGE_YUV_LIMITED_709, JPGE_YUV_FULL_709, JPGE_YUV_CUSTOM = 0, 1, 2, 3, 4
+
 #: subsampling modes (jpge.h JPGE_S*) -> (Y blocks across, Y blocks down) an MCU
 SUBSAMPLING = {420: (2, 2), 4200: (2, 2), 4201: (2, 2), 444: (1, 1), 422: (2, 1), 411: (4, 1)}
 
@@ -53,6 +58,7 @@ EXPORTS = (
     "jpge_get_timing", "jpge_reset_timing", "jpge_get_lanes", "jpge_set_restart_interval", "jpge_set_subsampling",
     "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info",
     "jpge_set_huffman", "jpge_get_huffman", "jpge_standard_huffman",
+    "jpge_set_yuv_transform", "jpge_get_yuv_transform", "jpge_yuv_preset",
     "jpge_max_jpeg_bytes", "jpge_quality_tables", "jpge_encode_rgb8", "jpge_encode_batch",
     "jpge_fdct_quant", "jpge_symbol_stats", "jpge_huffman_table", "jpge_huffman_text", "jpge_parse_ppm",
     "jpge_ppm_info", "jpge_encode_file", "jpge_encode_files", "jpge_synth_rgb8", "jpge_arai_constants",
@@ -133,6 +139,28 @@ class HuffSpec(ctypes.Structure):
         return s
 
 
+class YuvTransform(ctypes.Structure):
+    """jpge_yuv_transform: y_off and m[0..6] of the sample transform (jpge.h):
+    Y' = clamp((m0 (y - y_off) + m1 u) + m2 v, 0, 255) - 128, Cb' = clamp(m3 u + m4 v, -128, 127),
+    Cr' = clamp(m5 u + m6 v, -128, 127) with u = cb - 128, v = cr - 128."""
+    _fields_ = [("y_off", ctypes.c_double), ("m", ctypes.c_double * 7)]
+
+    def as_tuple(self) -> tuple[float, ...]:
+        """(y_off, m0, ..., m6)"""
+        return (float(self.y_off),) + tuple(float(x) for x in self.m)
+
+    @classmethod
+    def from_tuple(cls, t):
+        t = [float(x) for x in t]
+        if len(t) != 8:
+            raise ValueError("a sample transform has 8 coefficients: y_off, m0..m6")
+        s = cls()
+        s.y_off = t[0]
+        for i in range(7):
+            s.m[i] = t[1 + i]
+        return s
+
+
 class Timing(ctypes.Structure):
     _fields_ = [("fdct", ctypes.c_float), ("dc_stats", ctypes.c_float), ("entropy", ctypes.c_float),
                 ("total", ctypes.c_float), ("fdct_sum", ctypes.c_double), ("dc_stats_sum", ctypes.c_double),
@@ -171,6 +199,9 @@ def lib() -> ctypes.CDLL:
         L.jpge_set_huffman.argtypes = [vp, i32, ctypes.POINTER(HuffSpec)]
         L.jpge_get_huffman.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(HuffSpec)]
         L.jpge_standard_huffman.argtypes = [i32, ctypes.POINTER(HuffSpec)]
+        L.jpge_set_yuv_transform.argtypes = [vp, i32, ctypes.POINTER(YuvTransform)]
+        L.jpge_get_yuv_transform.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(YuvTransform)]
+        L.jpge_yuv_preset.argtypes = [i32, ctypes.POINTER(YuvTransform)]
         L.jpge_device_count.argtypes = [ctypes.POINTER(i32)]
         L.jpge_max_jpeg_bytes.restype = sz
         L.jpge_max_jpeg_bytes.argtypes = [u32, u32]
@@ -450,6 +481,13 @@ def standard_huffman(table: int) -> tuple[list[int], list[int]]:
     return s.as_tuple()
 
 
+def yuv_preset(preset: int) -> tuple[float, ...]:
+    """(y_off, m0, ..., m6) of a sample-transform preset (JPGE_YUV_*, not CUSTOM); host only."""
+    t = YuvTransform()
+    _check(lib().jpge_yuv_preset(int(preset), ctypes.byref(t)), "yuv_preset")
+    return t.as_tuple()
+
+
 def _huff_specs(specs):
     if specs is None:
         return None
@@ -663,6 +701,21 @@ class Encoder:
         _check(lib().jpge_get_huffman(self._ctx, ctypes.byref(m), arr), "get_huffman")
         return m.value, ([a.as_tuple() for a in arr] if m.value else None)
 
+    def set_yuv_transform(self, preset: int, coeffs=None) -> None:
+        """Sample transform of the following encodes of Y, Cb, Cr and gray frames (NV12, I420,
+        YUV444_PLANAR, GRAY8; encode*, encode_tensor_yuv, a 2-D encode_tensor, fdct_quant,
+        symbol_stats): JPGE_YUV_FULL_601 (the default: a sample v is v - 128), LIMITED_601,
+        LIMITED_709, FULL_709, or JPGE_YUV_CUSTOM with coeffs = (y_off, m0, ..., m6).  The
+        conversion runs inside the transform kernel; the RGB layouts ignore the setting."""
+        t = None if coeffs is None else YuvTransform.from_tuple(coeffs)
+        _check(lib().jpge_set_yuv_transform(self._ctx, int(preset), t), "set_yuv_transform")
+
+    def yuv_transform(self) -> tuple[int, tuple[float, ...]]:
+        """(preset, (y_off, m0, ..., m6)) as set."""
+        p, t = ctypes.c_int32(), YuvTransform()
+        _check(lib().jpge_get_yuv_transform(self._ctx, ctypes.byref(p), ctypes.byref(t)), "get_yuv_transform")
+        return p.value, t.as_tuple()
+
     def lanes(self) -> int:
         n = ctypes.c_int32()
         _check(lib().jpge_get_lanes(self._ctx, ctypes.byref(n)), "get_lanes")
@@ -769,8 +822,8 @@ class Encoder:
         return n if host_out is None else host_out[:n].tobytes()
 
     def encode_tensor_yuv(self, y, cbcr_or_cb, cr=None, quality: int = 50, out=None):
-        """One frame of full-range Y, Cb, Cr torch uint8 tensors (a decoder's surface) through
-        jpge_encode_rgb8, read in place: (H, W) + (ch, cw, 2) is NV12, (H, W) + two (ch, cw) is
+        """One frame of Y, Cb, Cr torch uint8 tensors (a decoder's surface; full-range BT.601
+        samples, or what set_yuv_transform says they are) through jpge_encode_rgb8, read in place: (H, W) + (ch, cw, 2) is NV12, (H, W) + two (ch, cw) is
         I420, (H, W) + two (H, W) is YUV444_PLANAR (ch, cw: H, W halved, rounded up).  The
         planes must be views of one allocation, all on one device, at offsets the layout can
         express (jpge.h): unit inner strides, the chroma after the Y plane, NV12's Cb,Cr rows
@@ -1066,6 +1119,14 @@ class Group:
             c = ctypes.c_void_p()
             _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
             _check(lib().jpge_set_huffman(c, int(mode), arr), "set_huffman")
+
+    def set_yuv_transform(self, preset: int, coeffs=None) -> None:
+        """Sample transform of every member's context (Encoder.set_yuv_transform): for encode_batch."""
+        t = None if coeffs is None else YuvTransform.from_tuple(coeffs)
+        for m in range(self.size()[0]):
+            c = ctypes.c_void_p()
+            _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
+            _check(lib().jpge_set_yuv_transform(c, int(preset), t), "set_yuv_transform")
 
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         """Config 4: frame i on member i mod N."""

@@ -180,7 +180,7 @@ const char* jpge_strerror(int s) {
     }
 }
 
-int jpge_version(void) { return 102; }
+int jpge_version(void) { return 103; }
 
 int jpge_device_count(int* n) {
     if (!n) return JPGE_E_ARG;
@@ -297,6 +297,28 @@ int jpge_get_huffman(jpge_ctx* ctx, int* mode, jpge_huff_spec specs[4]) {
 int jpge_standard_huffman(int table, jpge_huff_spec* spec) {
     if (table < 0 || table > 3 || !spec) return JPGE_E_ARG;
     std::memcpy(spec, &jpge::kAnnexKHuffman[table], sizeof(*spec));
+    return JPGE_OK;
+}
+
+static_assert(sizeof(jpge_yuv_transform) == sizeof(jpge::YuvXf) && sizeof(jpge_yuv_transform) == 64, "sample transform layout");
+
+int jpge_set_yuv_transform(jpge_ctx* ctx, int preset, const jpge_yuv_transform* custom) {
+    CtxUse use(ctx);
+    if (!use) return JPGE_E_ARG;
+    return ctx->enc->set_yuv_transform(preset, reinterpret_cast<const jpge::YuvXf*>(custom)) ? JPGE_E_ARG : JPGE_OK;
+}
+
+int jpge_get_yuv_transform(jpge_ctx* ctx, int* preset, jpge_yuv_transform* t) {
+    CtxUse use(ctx);
+    if (!use || !preset) return JPGE_E_ARG;
+    ctx->enc->yuv_transform(preset, reinterpret_cast<jpge::YuvXf*>(t));
+    return JPGE_OK;
+}
+
+int jpge_yuv_preset(int preset, jpge_yuv_transform* t) {
+    jpge::YuvXf x;
+    if (!t || !jpge::yuv_preset(preset, x)) return JPGE_E_ARG;
+    std::memcpy(t, &x, sizeof(*t));
     return JPGE_OK;
 }
 

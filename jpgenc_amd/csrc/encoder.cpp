@@ -454,6 +454,21 @@ int Encoder::set_input_format(int fmt, size_t plane_stride) {
     return kOk;
 }
 
+int Encoder::set_yuv_transform(int preset, const YuvXf* custom) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    YuvXf t;
+    if (const int st = yuv_setting_check(preset, custom, t)) return st;
+    yuv_preset_ = preset;
+    yuv_xf_ = t;
+    return kOk;
+}
+
+void Encoder::yuv_transform(int* preset, YuvXf* t) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    if (preset) *preset = yuv_preset_;
+    if (t) *t = yuv_xf_;
+}
+
 int Encoder::set_subsampling(int mode) {
     uint32_t yh, bpm, cf;
     if (!mode_shape(mode, yh, bpm, cf)) return kErrArg;
@@ -763,6 +778,12 @@ FdctArgs Encoder::fdct_args(Slot& s, int maxval, Slot* imp) {
     a.stride = s.in_stride;
     a.fmt = s.in_fmt;
     a.plane_stride = s.in_plane_stride;
+    // the sample transform of Y, Cb, Cr and gray frames (FULL_601: the kExact instances)
+    a.xf_on = (fmt_yuv(s.in_fmt) || fmt_gray(s.in_fmt)) && yuv_preset_ != kYuvFull601 ? 1u : 0u;
+    if (a.xf_on) {
+        a.xf[0] = yuv_xf_.y_off;
+        for (int i = 0; i < 7; ++i) a.xf[1 + i] = yuv_xf_.m[i];
+    }
     a.g = s.g;
     a.maxval = maxval;
     a.solo = lanes_.size() == 1;  // (several lanes: K1 runs beside other frames' kernels)

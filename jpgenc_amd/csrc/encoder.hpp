@@ -148,6 +148,13 @@ class Encoder {
     // the setting; specs (optional): the four tables of a fixed mode (optimal: untouched)
     void huffman(int* mode, HuffSpec* specs);
 
+    // Sample transform of the following Y, Cb, Cr and gray encodes (jpge.h JPGE_YUV_*,
+    // host_io.hpp YuvXf): FULL_601 (the default) takes a sample v as v - 128; the other
+    // presets, or CUSTOM with the caller's coefficients, convert each sample inside K1.
+    // The RGB layouts ignore the setting, and the header bytes do not depend on it.
+    int set_yuv_transform(int preset, const YuvXf* custom);
+    void yuv_transform(int* preset, YuvXf* t);
+
     int lanes() const { return (int)lanes_.size(); }
 
   private:
@@ -229,6 +236,8 @@ class Encoder {
     uint32_t huff_words_[4 * 256] = {};
     uint64_t huff_gen_ = 0;
     size_t plane_stride_ = 0;
+    int yuv_preset_ = kYuvFull601;  // sample transform (jpge_set_yuv_transform) and its coefficients
+    YuvXf yuv_xf_;
     // entropy workgroups: the override, else 512 for a single lane's lone frames (their
     // latency: -5 us at 4K) and seg_layout's default (384, or 2 tiles per workgroup under
     // 768 tiles) beside other lanes (+3% throughput) and for a single lane's frame sets

@@ -176,7 +176,9 @@ static_assert(kShape >= kShapeRgb8 && kShape <= kShapeGray, "JPGE_K1_SHAPE");
 // The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
 // layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
 // conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
-// takes each cell's top-left word: no chroma filter.  maxval is 255 (kExact instances only).
+// takes each cell's top-left word: no chroma filter.  maxval is 255.  Their !kExact instances
+// (FdctArgs::xf_on) convert each staged word by the context's sample transform (XfK below)
+// on its way to a double; nothing else differs.
 // The gray shape stages words that hold Y alone and has the row-8 kernel's one-component
 // instance only: 16 one-block MCUs per tile, the two Y rounds, no chroma rounds.
 constexpr bool kYuv = kShape >= kShapeNv12;
@@ -244,6 +246,38 @@ __device__ __forceinline__ void unpack_gray(const uint4& v0, uint32_t px[16]) {
 // a staged word's samples (exact: integers)
 __device__ __forceinline__ double yuv_y(uint32_t p) { return (double)(p & 0xFF) - 128.0; }
 __device__ __forceinline__ double yuv_c(uint32_t p, int comp) { return (double)((p >> (8 * comp)) & 0xFF) - 128.0; }
+
+// The sample transform of the Y, Cb, Cr shapes' !kExact instances (host_io.hpp YuvXf: limited
+// range, BT.709 or the caller's coefficients): wave-uniform, held in scalar registers.  Every
+// product and sum is rounded on its own, in the order written (no contraction: the bytes
+// are defined by it, as ycc_ref_y's are).  The clamps keep a converted sample inside the
+// interval of an 8-bit one, [-128, 127], whatever the input: the coefficient bounds of the
+// entropy stage (DC category <= 11, AC size <= 10) rest on it.
+struct XfK {
+    double y_off, m0, m1, m2, m3, m4, m5, m6;
+};
+__device__ __forceinline__ double xf_clamp_y(double s) { return __builtin_fmin(__builtin_fmax(s, 0.0), 255.0) - 128.0; }
+// Y' of a word's Y byte, given the products t1 = m1 u, t2 = m2 v of its chroma
+__device__ __forceinline__ double xf_y(const XfK& k, uint32_t p, double t1, double t2) {
+    const double yc = (double)(p & 0xFF) - k.y_off;
+    if constexpr (kGray) return xf_clamp_y(k.m0 * yc);  // (one component: y_off and m0 only)
+    return xf_clamp_y((k.m0 * yc + t1) + t2);
+}
+__device__ __forceinline__ double xf_y(const XfK& k, uint32_t p) {
+    return xf_y(k, p, k.m1 * yuv_c(p, 1), k.m2 * yuv_c(p, 2));
+}
+// Cb' (ku = m3, kv = m4) or Cr' (m5, m6) of a word
+__device__ __forceinline__ double xf_c(uint32_t p, double ku, double kv) {
+    const double s = ku * yuv_c(p, 1) + kv * yuv_c(p, 2);
+    return __builtin_fmin(__builtin_fmax(s, -128.0), 127.0);
+}
+// the coefficients of a's transform, by scalar loads (the prologue issues no vector load,
+// see above), pinned: the tile loop would otherwise reload them
+__device__ __forceinline__ XfK xf_load(const FdctArgs& a) {
+    XfK k{a.xf[0], a.xf[1], a.xf[2], a.xf[3], a.xf[4], a.xf[5], a.xf[6], a.xf[7]};
+    asm volatile("" : "+s"(k.y_off), "+s"(k.m0), "+s"(k.m1), "+s"(k.m2), "+s"(k.m3), "+s"(k.m4), "+s"(k.m5), "+s"(k.m6));
+    return k;
+}
 
 // One pixel of the Y, Cb, Cr shapes' clamped edge path: row sy, column sx (inside the
 // frame); a 4:2:0 layout's chroma of the pixel's cell (inside the chroma plane: the
@@ -361,6 +395,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         sel4_ = a.fmt == kFmtBgra8 ? kSelBgrx : kSelRgbx;
         asm volatile("" : "+s"(sel4_));
     }
+    XfK xf{};  // (the Y, Cb, Cr shapes' !kExact instances)
+    if constexpr (kYuv && !kExact) xf = xf_load(a);
     constexpr int kK1Threads = kWaves * 64;
     __shared__ K1Lds<kWaves> lds;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;  // wv: 0..15
@@ -479,6 +515,18 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         for (int u = 0; u < 8; ++u) iq[u] = lds.invq[qb][j * kQRow + u];
     };
     auto y_inputs = [&](const uint32_t p[8], double x[8]) {
+        if constexpr (kYuv && !kExact) {
+            // the sample transform; a 4:2:0 layout's rows 2r, 2r + 1 lie in one cell (yrow0 is
+            // even), so the chroma bytes are converted and scaled once per pair
+            constexpr int n = kYuv420 ? 2 : 1;
+#pragma unroll
+            for (int i = 0; i < 8; i += n) {
+                const double t1 = xf.m1 * yuv_c(p[i], 1), t2 = xf.m2 * yuv_c(p[i], 2);
+#pragma unroll
+                for (int r = 0; r < n; ++r) x[i + r] = xf_y(xf, p[i + r], t1, t2);
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) x[i] = kYuv ? yuv_y(p[i]) : kExact ? ycc_exact_y(p[i]) : ycc_ref_y(p[i], scale);
     };
@@ -528,6 +576,12 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
             return;
         }
         const double kr = ccomp ? kCrR : kCbR, kg = ccomp ? kCrG : kCbG, kb = ccomp ? kCrB : kCbB;
+        const double ku = ccomp ? xf.m5 : xf.m3, kv = ccomp ? xf.m6 : xf.m4;  // (Y, Cb, Cr words)
+        // a pixel's chroma: the colour conversion, or the sample transform of a Y, Cb, Cr word
+        auto ref_c = [&](uint32_t w) {
+            if constexpr (kYuv) return xf_c(w, ku, kv);
+            else return ycc_ref_c(w, scale, kr, kg, kb);
+        };
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const uint2 t0 = c[2 * i], t1 = c[2 * i + 1];
@@ -535,20 +589,20 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
             if (kFilt == kFiltS420) {
                 // subsample(S420), Image.cpp:279-286: mask {1, 0} on even rows only, the
                 // top-left sample (the mask's 0 * b adds a zero)
-                x[i] = ycc_ref_c(t0.x, scale, kr, kg, kb);
+                x[i] = ref_c(t0.x);
             } else if (kFilt == kFiltS420lm) {
                 // subsample(S420_lm), Image.cpp:297-306, 218-224: (a + c) / 2 of the left
                 // samples of both rows
-                double v = ycc_ref_c(t0.x, scale, kr, kg, kb);
-                v += ycc_ref_c(t1.x, scale, kr, kg, kb);
+                double v = ref_c(t0.x);
+                v += ref_c(t1.x);
                 x[i] = v / 2;
             } else {
                 // subsample(S420_m), Image.cpp:207-224: ((0+a+b) + (0+c+d)) / 4
                 double top = 0.0, bot = 0.0;
-                top += ycc_ref_c(t0.x, scale, kr, kg, kb);
-                top += ycc_ref_c(t0.y, scale, kr, kg, kb);
-                bot += ycc_ref_c(t1.x, scale, kr, kg, kb);
-                bot += ycc_ref_c(t1.y, scale, kr, kg, kb);
+                top += ref_c(t0.x);
+                top += ref_c(t0.y);
+                bot += ref_c(t1.x);
+                bot += ref_c(t1.y);
                 x[i] = (top + bot) / 4;
             }
         }
@@ -697,6 +751,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         sel4_ = a.fmt == kFmtBgra8 ? kSelBgrx : kSelRgbx;
         asm volatile("" : "+s"(sel4_));
     }
+    XfK xf{};  // (the Y, Cb, Cr shapes' !kExact instances)
+    if constexpr (kYuv && !kExact) xf = xf_load(a);
     constexpr int kK1Threads = kWaves * 64;
     constexpr uint32_t kMcus = 16 / kYh;            // MCUs per tile
     static_assert(!kGray || kYh == 1, "one component: one-block MCUs");
@@ -834,10 +890,12 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
             double x[8];
             if (comp == 0) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) x[i] = kYuv ? yuv_y(p[i]) : kExact ? ycc_exact_y(p[i]) : ycc_ref_y(p[i], scale);
-            } else if constexpr (kYuv) {  // the kept sample itself
+                for (int i = 0; i < 8; ++i)
+                    x[i] = kYuv ? (kExact ? yuv_y(p[i]) : xf_y(xf, p[i])) : kExact ? ycc_exact_y(p[i]) : ycc_ref_y(p[i], scale);
+            } else if constexpr (kYuv) {  // the kept sample itself, or its transform
+                const double ku = comp == 2 ? xf.m5 : xf.m3, kv = comp == 2 ? xf.m6 : xf.m4;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) x[i] = yuv_c(p[i], comp);
+                for (int i = 0; i < 8; ++i) x[i] = kExact ? yuv_c(p[i], comp) : xf_c(p[i], ku, kv);
             } else {
                 const double kr = comp == 2 ? kCrR : kCbR, kg = comp == 2 ? kCrG : kCbG, kb = comp == 2 ? kCrB : kCbB;
 #pragma unroll
@@ -901,14 +959,13 @@ bool k1_whole_cu(const Geometry& g, bool solo) { return solo && k1_tiles(g) >= k
 template <int kYh, int kN>
 static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     const FdctArgs& a = fs.a[0];
-    const bool ex = a.maxval == 255;
+    // (Y, Cb, Cr samples are 8-bit, maxval 255: their !kExact instances are the sample transform's)
+    const bool ex = kYuv ? a.xf_on == 0 : a.maxval == 255;
     if (k1_whole_cu(a.g, a.solo)) {
         if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
-        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
     } else {
         if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
-        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     }
 }
@@ -916,14 +973,13 @@ static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, h
 template <int kFilt, int kN>
 static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     const FdctArgs& a = fs.a[0];
-    const bool ex = a.maxval == 255;
+    // (Y, Cb, Cr samples are 8-bit, maxval 255: their !kExact instances are the sample transform's)
+    const bool ex = kYuv ? a.xf_on == 0 : a.maxval == 255;
     if (k1_whole_cu(a.g, a.solo)) {
         if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
-        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
     } else {
         if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
-        else if constexpr (kYuv) return hipErrorInvalidValue;  // (Y, Cb, Cr samples are 8-bit: maxval 255)
         else return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     }
 }
@@ -1009,7 +1065,7 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
             (uint64_t)m.g.nblocks() * 128 >= kOob)
             return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
-            fmt_shape(m.fmt) != fmt_shape(a.fmt) ||
+            fmt_shape(m.fmt) != fmt_shape(a.fmt) || (m.xf_on != 0) != (a.xf_on != 0) ||
             m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs))
             return hipErrorInvalidValue;
     }

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -311,6 +312,51 @@ int huff_setting_check(int mode, const HuffSpec* specs) {
     if (!specs) return kErrArg;
     for (int t = 0; t < 4; ++t)
         if (!huff_spec_valid(specs[t], (t & 1) != 0)) return kErrArg;
+    return kOk;
+}
+
+// The presets of the sample transform.  With luma weights (kr, kb), kg = 1 - kr - kb, a
+// matrix's Y, Cb, Cr are Y = kr R + kg G + kb B, Cb = (B - Y) / (2 (1 - kb)),
+// Cr = (R - Y) / (2 (1 - kr)).  A *_709 preset carries A601 . inverse(A709): both matrices
+// send grey to (Y, 0, 0), so its first column is (1, 0, 0) and seven entries remain, the
+// images of a unit of BT.709 Cb and of Cr.  Studio swing stores 219 Y / 255 + 16 and
+// 224 C / 255 + 128: y_off 16, the Y column scaled by 255/219, the chroma columns by 255/224.
+bool yuv_preset(int preset, YuvXf& t) {
+    if (preset < kYuvFull601 || preset > kYuvFull709) return false;
+    const bool limited = preset == kYuvLimited601 || preset == kYuvLimited709;
+    const bool from709 = preset == kYuvLimited709 || preset == kYuvFull709;
+    const double sy = limited ? 255.0 / 219.0 : 1.0, sc = limited ? 255.0 / 224.0 : 1.0;
+    t = YuvXf();
+    t.y_off = limited ? 16.0 : 0.0;
+    t.m[0] = sy;
+    t.m[3] = t.m[6] = sc;
+    if (from709) {
+        const double kr6 = 0.299, kb6 = 0.114, kg6 = 1.0 - kr6 - kb6;
+        const double kr9 = 0.2126, kb9 = 0.0722, kg9 = 1.0 - kr9 - kb9;
+        // R, G, B of a unit of BT.709 Cb, then of Cr
+        const double rgb[2][3] = {{0.0, -2.0 * kb9 * (1.0 - kb9) / kg9, 2.0 * (1.0 - kb9)},
+                                  {2.0 * (1.0 - kr9), -2.0 * kr9 * (1.0 - kr9) / kg9, 0.0}};
+        for (int c = 0; c < 2; ++c) {
+            const double y = kr6 * rgb[c][0] + kg6 * rgb[c][1] + kb6 * rgb[c][2];
+            t.m[1 + c] = y * sc;
+            t.m[3 + c] = (rgb[c][2] - y) / (2.0 * (1.0 - kb6)) * sc;
+            t.m[5 + c] = (rgb[c][0] - y) / (2.0 * (1.0 - kr6)) * sc;
+        }
+    }
+    return true;
+}
+
+int yuv_setting_check(int preset, const YuvXf* custom, YuvXf& t) {
+    if (preset == kYuvCustom) {
+        if (!custom) return kErrArg;
+        t = *custom;
+    } else if (!yuv_preset(preset, t)) {
+        return kErrArg;
+    }
+    // (the comparisons are false for a NaN)
+    if (!(t.y_off >= 0.0 && t.y_off <= 255.0)) return kErrArg;
+    for (const double m : t.m)
+        if (!(std::fabs(m) <= 4.0)) return kErrArg;
     return kOk;
 }
 

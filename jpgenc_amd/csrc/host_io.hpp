@@ -87,6 +87,24 @@ int huff_setting_check(int mode, const HuffSpec* specs);
 // length, plus one, shifted left.
 void huff_spec_table(const HuffSpec& spec, HuffTable& out);
 
+// ---- sample transform of Y, Cb, Cr input (jpge_set_yuv_transform; an addition) ----
+// jpge_yuv_transform, the same layout.  With bytes (y, cb, cr) of a pixel, yc = y - y_off,
+// u = cb - 128, v = cr - 128 (exact), the planes that enter the pipeline are
+//   Y'  = min(max((m0 yc + m1 u) + m2 v, 0), 255) - 128
+//   Cb' = min(max(m3 u + m4 v, -128), 127),  Cr' = min(max(m5 u + m6 v, -128), 127)
+// every product and sum rounded to fp64 on its own, in this order (K1, fdct.hip XfK).
+struct YuvXf {
+    double y_off = 0;
+    double m[7] = {1, 0, 0, 1, 0, 0, 1};
+};
+constexpr int kYuvFull601 = 0, kYuvLimited601 = 1, kYuvLimited709 = 2, kYuvFull709 = 3, kYuvCustom = 4;
+// A preset's coefficients (false: no such preset; kYuvCustom has none).
+bool yuv_preset(int preset, YuvXf& t);
+// jpge_set_yuv_transform's argument check and the setting's coefficients: kOk, or kErrArg
+// for an unknown preset, kYuvCustom without a struct, a non-finite value, y_off outside
+// 0..255 or an |m[i]| above 4.
+int yuv_setting_check(int preset, const YuvXf* custom, YuvXf& t);
+
 // Deterministic synthetic RGB8 frame (integer-only, identical on every host):
 // kind 0 = smooth gradients + texture + noise (photo-like), 1 = uniform random
 // bytes (worst-case symbol statistics), 2 = flat colour.

@@ -130,7 +130,13 @@ struct FdctArgs {
     // input layout (kFmt*); planar: plane c's rows start at rgb + c * plane_stride
     // (NV12, I420: the chroma starts at rgb + plane_stride, see fmt_chroma_pitch)
     int fmt = kFmtRgb8;
+    // 1: the Y, Cb, Cr and gray shapes convert each sample by xf (jpge_set_yuv_transform, a
+    // preset other than FULL_601): their !kExact instances.  The other shapes ignore it.
+    // (in the padding after fmt; xf at the block's end: no earlier field moves)
+    uint32_t xf_on = 0;
     uint64_t plane_stride = 0;
+    // y_off, m0..m6 (host_io.hpp YuvXf); fetched with scalar loads, like q
+    alignas(16) double xf[8] = {0, 1, 0, 0, 1, 0, 0, 1};
 };
 
 // Stripe context of a frame (a row stripe of a larger image); the

@@ -189,6 +189,12 @@ int env_int(const char* name, int dflt, int lo, int hi) {
     return x < lo ? lo : x > hi ? hi : (int)x;
 }
 
+int64_t thread_cpu_ns() {  // the calling thread's CPU time (JPGE_CPU_PROF)
+    timespec t;
+    clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t);
+    return (int64_t)t.tv_sec * 1000000000 + t.tv_nsec;
+}
+
 constexpr size_t kTabBytes = 4 * 256 * 4;  // code tables as uploaded
 constexpr size_t kHdrMax = 4096;           // headers SOI .. SOS (<= 20 + 2*69 + 19 + 4*277 + 14)
 
@@ -370,6 +376,16 @@ struct Encoder::Slot {
     } fixed;
 
     uint32_t* gate() const { return reinterpret_cast<uint32_t*>(h_result + 6); }
+
+    // The carried export of `e`: its code kernel takes exp's histograms (a later frame's)
+    // to the host on the way; nullptr: none.
+    static void carry_export(EntropyArgs& e, const Slot* exp) {
+        e.exp_hist = exp ? exp->hist : HistPtrs{};
+        e.exp_cnt = exp ? exp->d_hist_host->cnt : nullptr;
+        e.exp_key = exp ? exp->d_hist_host->key : nullptr;
+        e.exp_seq = exp ? &exp->d_hist_host->seq : nullptr;
+        e.exp_seqv = exp ? exp->seq : 0;
+    }
 
     ~Slot() {
         hipFree(d_in); hipFree(d_coef); hipFree(d_ctl); hipFree(d_ubuf);
@@ -861,11 +877,7 @@ EntropyArgs Encoder::entropy_args(Slot& s) {
         e.seg_index0 = s.rst.mcu0 / s.rst.mcus;
         e.seg_markers0 = e.seg_index0 > 0 ? 1u : 0u;
     }
-    e.exp_hist = HistPtrs{};
-    e.exp_cnt = nullptr;
-    e.exp_key = nullptr;
-    e.exp_seq = nullptr;
-    e.exp_seqv = 0;
+    Slot::carry_export(e, nullptr);
     e.dbg = d_dbg_ ? d_dbg_ + 2 * 65536 * kStampSlots : nullptr;
     return e;
 }
@@ -1036,19 +1048,14 @@ int Encoder::build_tables(Slot& s, bool parallel, TableHelper* helper) {
                                s.inline_tables ? s.guess_hist : nullptr))
         return w;
     if (lat_prof_) lat_hist_seen_ = std::chrono::steady_clock::now();
-    auto thread_ns = [] {
-        timespec t;
-        clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t);
-        return (int64_t)t.tv_sec * 1000000000 + t.tv_nsec;
-    };
-    const int64_t t0 = cpu_prof_ ? thread_ns() : 0;
+    const int64_t t0 = cpu_prof_ ? thread_cpu_ns() : 0;
     // (the tables read the mapped export in place: the keys stay inverted, and only the
     // present symbols' keys are read)
-    const int64_t t1 = cpu_prof_ ? thread_ns() : 0;
+    const int64_t t1 = cpu_prof_ ? thread_cpu_ns() : 0;
     const int r = build_tables_from(s, s.h_hist->cnt, s.h_hist->key, parallel, /*inverted=*/true, helper);
     if (cpu_prof_) {
         cpu_read_ns_.fetch_add(t1 - t0, std::memory_order_relaxed);
-        cpu_build_ns_.fetch_add(thread_ns() - t1, std::memory_order_relaxed);
+        cpu_build_ns_.fetch_add(thread_cpu_ns() - t1, std::memory_order_relaxed);
         cpu_builds_.fetch_add(1, std::memory_order_relaxed);
     }
     return r;
@@ -1058,12 +1065,7 @@ int Encoder::build_tables(Slot& s, bool parallel, TableHelper* helper) {
 // image's real dimensions in SOF0), into the slot's pinned staging buffer.
 int Encoder::build_tables_from(Slot& s, const uint32_t* cnt_all, const uint64_t* first_all, bool parallel,
                                bool inverted, TableHelper* helper) {
-    auto thread_ns = [] {
-        timespec t;
-        clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t);
-        return (int64_t)t.tv_sec * 1000000000 + t.tv_nsec;
-    };
-    const int64_t t0 = cpu_prof_ ? thread_ns() : 0;
+    const int64_t t0 = cpu_prof_ ? thread_cpu_ns() : 0;
     s.fixed.gen = 0;  // (the slot's table buffers get this frame's own tables)
     HuffTable tabs[4];
     int ok[4] = {0, 0, 0, 0};
@@ -1085,12 +1087,12 @@ int Encoder::build_tables_from(Slot& s, const uint32_t* cnt_all, const uint64_t*
     } else {
         parallel_for(4, parallel ? 4 : 1, one);
     }
-    const int64_t t1 = cpu_prof_ ? thread_ns() : 0;
+    const int64_t t1 = cpu_prof_ ? thread_cpu_ns() : 0;
     for (int t = 0; t < (gray ? 2 : 4); ++t)
         if (ok[t])
             for (int i = 0; i < 256; ++i)
                 s.h_tab[t * 256 + i] = ((uint32_t)tabs[t].len[i] << 16) | (tabs[t].code[i] & 0xFFFF);
-    const int64_t t2 = cpu_prof_ ? thread_ns() : 0;
+    const int64_t t2 = cpu_prof_ ? thread_cpu_ns() : 0;
     const int bad = !(ok[0] & ok[1] & ok[2] & ok[3]);
     uint64_t nsym = 0;
     for (int i = 0; i < 1024; ++i) nsym += cnt_all[i];
@@ -1117,7 +1119,7 @@ int Encoder::build_tables_from(Slot& s, const uint32_t* cnt_all, const uint64_t*
     if (cpu_prof_) {
         cpu_part_ns_[0].fetch_add(t1 - t0, std::memory_order_relaxed);
         cpu_part_ns_[1].fetch_add(t2 - t1, std::memory_order_relaxed);
-        cpu_part_ns_[2].fetch_add(thread_ns() - t2, std::memory_order_relaxed);
+        cpu_part_ns_[2].fetch_add(thread_cpu_ns() - t2, std::memory_order_relaxed);
     }
     if (s.out_cap && s.out_cap < s.hdr_len + 2) return kErrNoSpace;
     return kOk;
@@ -1126,6 +1128,12 @@ int Encoder::build_tables_from(Slot& s, const uint32_t* cnt_all, const uint64_t*
 // Tables + headers to the device by a copy (when no transform kernel carries them).
 int Encoder::import_tables_copy(Slot& s) {
     JPGE_HIP(hipMemcpyAsync(s.d_tab, s.h_tab, kTabBytes + s.hdr_len, hipMemcpyHostToDevice, s.stream));
+    return kOk;
+}
+
+int Encoder::export_hist(Slot& s) {
+    JPGE_HIP(launch_hist_export(s.hist, s.d_hist_host->cnt, s.d_hist_host->key, &s.d_hist_host->seq, s.seq, s.stream));
+    s.export_queued.store(1, std::memory_order_release);
     return kOk;
 }
 
@@ -1140,11 +1148,7 @@ int Encoder::launch_entropy_phase(Slot& s, Slot* exp, bool lone, int parts) {
     if (lone && lanes_.size() == 1)
         e.pack_done = reinterpret_cast<uint32_t*>(s.d_ctl + CtlLayout(slot_layout(s).grid()).done + kPackDoneOff);
     if (parts == 3) s.h_result[2] = 0;  // (the slot's previous entropy kernel finished before phase1; gated: encode())
-    e.exp_hist = exp ? exp->hist : HistPtrs{};
-    e.exp_cnt = exp ? exp->d_hist_host->cnt : nullptr;
-    e.exp_key = exp ? exp->d_hist_host->key : nullptr;
-    e.exp_seq = exp ? &exp->d_hist_host->seq : nullptr;
-    e.exp_seqv = exp ? exp->seq : 0;
+    Slot::carry_export(e, exp);
     const KTimer tc{s.ev[4], s.ev[5]}, tp{s.ev[6], s.ev[7]};
     if (parts & 1) JPGE_HIP(launch_entropy_code(e, s.stream, s.timed ? &tc : nullptr));
     if (parts & 2) JPGE_HIP(launch_entropy_pack(e, s.stream, s.timed ? &tp : nullptr));
@@ -1288,21 +1292,7 @@ int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], ui
         if (!st) st = finish(s, f, flags);
     }
     if (lat_prof_) T[4] = clk::now();
-    // Every output byte is in place.  Device output on a 1-lane encoder: the result word is
-    // written once every pack workgroup's (write-through) stores have completed, so the
-    // kernel's formal end is not awaited (the stream orders the context's next work after
-    // it; ~9 us).  Host
-    // output: the copy queued by finish(), awaited by spinning as a batch lane's end (a
-    // blocking stream synchronisation adds tens of us of wake-up).
-    const bool await_end = st || !(flags & kFlagDeviceOutput) || lanes_.size() != 1;
-    if (await_end) {
-        if (hipEventRecord(lanes_[0]->done, s.stream) != hipSuccess) {
-            hipStreamSynchronize(s.stream);
-        } else {
-            const hipError_t w = wait_event(lanes_[0]->done);
-            if (w != hipSuccess && !st) st = kErrHip;
-        }
-    }
+    st = await_call_end(s, flags, st);
     if (lat_prof_ && !st) {
         T[5] = clk::now();
         auto ns = [](clk::time_point a, clk::time_point b) {
@@ -1330,17 +1320,23 @@ int Encoder::encode_fixed(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[6
     if (!st) st = launch_entropy_phase(s, nullptr, /*lone=*/true);
     if (st) s.fixed.gen = 0;  // (the tables may not have reached the device)
     if (!st) st = finish(s, f, flags);
-    // (every output byte in place: as encode())
-    const bool await_end = st || !(flags & kFlagDeviceOutput) || lanes_.size() != 1;
-    if (await_end) {
-        if (hipEventRecord(lanes_[0]->done, s.stream) != hipSuccess) {
-            hipStreamSynchronize(s.stream);
-        } else {
-            const hipError_t w = wait_event(lanes_[0]->done);
-            if (w != hipSuccess && !st) st = kErrHip;
-        }
-    }
+    st = await_call_end(s, flags, st);
     f.status = st;
+    return st;
+}
+
+// Every output byte of a single image is in place.  Device output on a 1-lane encoder: the
+// result word is written once every pack workgroup's (write-through) stores have
+// completed, so the kernel's formal end is not awaited (the stream orders the context's
+// next work after it; ~9 us).  Host output: the copy queued by finish(), awaited by
+// spinning as a batch lane's end (a blocking stream synchronisation adds tens of us of
+// wake-up).
+int Encoder::await_call_end(Slot& s, uint32_t flags, int st) {
+    if (!st && (flags & kFlagDeviceOutput) && lanes_.size() == 1) return st;
+    if (hipEventRecord(lanes_[0]->done, s.stream) != hipSuccess)
+        hipStreamSynchronize(s.stream);
+    else if (wait_event(lanes_[0]->done) != hipSuccess && !st)
+        st = kErrHip;
     return st;
 }
 
@@ -1351,8 +1347,7 @@ int Encoder::encode_batch(FrameDesc* fr, int n, const uint8_t qy[64], const uint
     for (int i = 0; i < n; ++i) fr[i].status = 0;
     if (n <= 0) return kOk;
     // (fixed Huffman tables: the lanes run the pipeline without the host in the middle)
-    const bool fixed = huff_mode_ != 0;
-    flags = (flags & ~kFlagFixedTables) | (fixed ? kFlagFixedTables : 0u);
+    flags = (flags & ~kFlagFixedTables) | (huff_mode_ ? kFlagFixedTables : 0u);
     // Frames are dealt dynamically: a lane takes the batch's next frame (or frame set)
     // when its pipeline has room, so lanes finish together.  Lane 0 runs on the calling
     // thread.
@@ -1362,16 +1357,14 @@ int Encoder::encode_batch(FrameDesc* fr, int n, const uint8_t qy[64], const uint
         if (const int st = add_slots(*lanes_[l], (lookahead_ + drain_lag_ + 1) * set)) return st;
     std::atomic<int> next{0};
     for (int l = 1; l < nl; ++l)
-        lanes_[l]->post([this, l, fr, n, &next, set, qy, qc, flags, fixed] {
+        lanes_[l]->post([this, l, fr, n, &next, set, qy, qc, flags] {
             hipSetDevice(device_);
-            return fixed ? run_lane_fixed(*lanes_[l], fr, n, &next, set, qy, qc, flags)
-                         : run_lane(*lanes_[l], fr, n, &next, set, qy, qc, flags);
+            return run_lane(*lanes_[l], fr, n, &next, set, qy, qc, flags);
         });
     // (napping on the calling thread: ~1 us timer slack for the call, restored after)
     const long slack = nap_ ? prctl(PR_GET_TIMERSLACK, 0, 0, 0, 0) : -1;
     if (slack > 0) prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);
-    int st = fixed ? run_lane_fixed(*lanes_[0], fr, n, &next, set, qy, qc, flags)
-                   : run_lane(*lanes_[0], fr, n, &next, set, qy, qc, flags);
+    int st = run_lane(*lanes_[0], fr, n, &next, set, qy, qc, flags);
     if (slack > 0) prctl(PR_SET_TIMERSLACK, (unsigned long)slack, 0, 0, 0);
     const auto t_lane0 = std::chrono::steady_clock::now();
     for (int l = 1; l < nl; ++l) {
@@ -1418,37 +1411,166 @@ int Encoder::batch_set_size(const FrameDesc* fr, int n) const {
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(kMaxSet, k));
 }
 
-int Encoder::run_lane(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* next, int set, const uint8_t qy[64],
-                      const uint8_t qc[64], uint32_t flags) {
-    const int S = (int)ln.slots.size() / set;  // slot sets (add_slots: >= lookahead + drain lag + 1)
-    // Pipeline step t handles frame set t of this lane: frames mine[t*set ..], each in
-    // slot (t mod S) * set + member.  Only the lane's last set may be short.
+// A lane's state for one batch, and the pipeline's steps over it; run_lane puts the steps
+// in their order.  Pipeline step t handles frame set t of this lane: frames mine[t*set ..],
+// each in slot (t mod S) * set + member.  Only the lane's last set may be short.  Arrays of
+// a set's slots are indexed by member; a null entry is a member that is not taking part.
+struct Encoder::LaneRun {
+    Encoder& enc;
+    Lane& ln;
+    FrameDesc* const frames;
+    const int total;
+    std::atomic<int>* const next;
+    const int set;
+    const uint8_t* const qy;
+    const uint8_t* const qc;
+    const uint32_t flags;
+    const bool fixed;       // fixed Huffman tables (kFlagFixedTables)
+    const int S;            // slot sets (add_slots: >= lookahead + drain lag + 1)
     std::vector<int> mine;  // batch indices of the frames this lane took, in its order
-    mine.reserve(total);
-    auto members = [&](int t) { return std::min(set, (int)mine.size() - t * set); };
-    auto frame = [&](int t, int m) -> FrameDesc& { return frames[mine[t * set + m]]; };
-    auto slot = [&](int t, int m) -> Slot& { return *ln.slots[(t % S) * set + m]; };
+    // Per-image tables: this lane's frames whose tables are not built yet.  The lane's waits
+    // build any whose histograms are in (the ~25 us of a 1080p frame's tables fill a wait
+    // instead of a worker's polling and hand-off), and a frame's entropy launch builds its
+    // own if they are still missing.
+    std::vector<Slot*> pend;
+    int n = 0;         // sets taken so far
+    bool open = true;  // the batch may still have frames
     int first_err = kOk;
-    auto note = [&](int t, int m, int st) {
+
+    LaneRun(Encoder& e, Lane& l, FrameDesc* fr, int tot, std::atomic<int>* nx, int st, const uint8_t* y,
+            const uint8_t* c, uint32_t fl)
+        : enc(e), ln(l), frames(fr), total(tot), next(nx), set(st), qy(y), qc(c), flags(fl),
+          fixed((fl & kFlagFixedTables) != 0), S((int)l.slots.size() / st) {
+        mine.reserve(total);
+    }
+    int members(int t) const { return std::min(set, (int)mine.size() - t * set); }
+    FrameDesc& frame(int t, int m) const { return frames[mine[t * set + m]]; }
+    Slot& slot(int t, int m) const { return *ln.slots[(t % S) * set + m]; }
+    void note(int t, int m, int st) {
+        if (st && fixed) slot(t, m).fixed.gen = 0;  // (its tables may not have reached the device)
         if (st && !frame(t, m).status) frame(t, m).status = st;
         if (st && !first_err) first_err = st;
-    };
-    // Software pipeline on the lane's stream (steps are lane-local).  Step i queues
-    //   K1(i) [carrying set j = i-L's tables + headers to the device], K2(i),
-    //   then set j's entropy kernels [the code kernel carrying set i's histograms to
-    //   the host for a table worker],
-    // so the host builds a set's tables while the GPU works through the L sets queued
-    // ahead of its entropy launch; set i-L-D is drained D steps after that launch (about
-    // D sets of queued GPU work while the host waits).  Member m of one set pairs with
-    // member m of the other for the carried duties.  The pipeline's edges fall back to a
-    // standalone export kernel and a table copy.
-    const int L = lookahead_, D = drain_lag_;
-    // This lane's frames whose tables are not built yet: the lane's waits build any whose
-    // histograms are in (the ~25 us of a 1080p frame's tables fill a wait instead of a
-    // worker's polling and hand-off), and a frame's entropy launch builds its own if they
-    // are still missing.
-    std::vector<Slot*> pend;
-    pend.reserve((size_t)(L + D + 2) * set);
+    }
+    // Step i has room for a new set: take the batch's next frames.
+    void take(int i) {
+        if (!open || i != n) return;
+        const int g = next->fetch_add(set, std::memory_order_relaxed);
+        if (g < total) {
+            for (int m = 0; m < set && g + m < total; ++m) mine.push_back(g + m);
+            ++n;
+        } else {
+            open = false;
+        }
+    }
+
+    // Queue K1 and K2 of set i into out[].  imp[m]: the slot whose tables and headers member
+    // m's K1 carries to the device (fixed tables: none).  lone_exports: a single frame's K2
+    // exports its own histograms when it has no partner (whose code kernel would).  A
+    // single frame takes the 1-member kernel instances, a set one launch per kernel.
+    void queue_phase1(int i, Slot* const* imp, bool lone_exports, Slot** out) {
+        if (set == 1) {
+            Slot& s = slot(i, 0);
+            note(i, 0, enc.phase1(s, frame(i, 0), qy, qc, flags, imp[0], lone_exports && !imp[0]));
+            if (!frame(i, 0).status) out[0] = &s;
+            return;
+        }
+        Slot* ss[kMaxSet];
+        FdctArgs fa[kMaxSet];
+        StatsArgs sa[kMaxSet];
+        int ms[kMaxSet], ok = 0;
+        for (int m = 0; m < members(i); ++m) {
+            Slot& s = slot(i, m);
+            const int st = enc.prep1(s, frame(i, m), qy, qc, flags, imp[m], fa[ok], sa[ok]);
+            note(i, m, st);
+            if (st) continue;
+            ss[ok] = &s;
+            ms[ok++] = m;
+        }
+        if (!ok) return;
+        const int st = enc.phase1_set(ss, ok, fa, sa);
+        for (int q = 0; q < ok; ++q) {
+            note(i, ms[q], st);
+            if (!st) out[ms[q]] = ss[q];
+        }
+    }
+
+    // Queue the entropy kernels of set t's members in s[] (tables on the device or on their
+    // way): one launch per kernel for the set, or frame by frame (a single frame; a member
+    // its code kernel does not place).  carry (or null): member m's code kernel exports
+    // carry[m]'s histograms on the way, which is noted there.  A member whose launch failed
+    // leaves s[].
+    void queue_entropy(int t, Slot** s, Slot* const* carry) {
+        EntropyArgs ea[kMaxSet];
+        int ms[kMaxSet], ne = 0;
+        bool as_set = set > 1;
+        Slot* tm = nullptr;  // (a sampled set's member: its events time the launches)
+        for (int m = 0; m < members(t); ++m) {
+            if (!s[m]) continue;
+            ea[ne] = enc.entropy_args(*s[m]);
+            if (carry && carry[m]) Slot::carry_export(ea[ne], carry[m]);
+            as_set = as_set && ea[ne].done;
+            if (s[m]->timed && !tm) tm = s[m];
+            ms[ne++] = m;
+        }
+        if (!ne) return;
+        if (as_set) {
+            for (int q = 0; q < ne; ++q) s[ms[q]]->h_result[2] = 0;
+            const KTimer tc{tm ? tm->ev[4] : nullptr, tm ? tm->ev[5] : nullptr};
+            const KTimer tp{tm ? tm->ev[6] : nullptr, tm ? tm->ev[7] : nullptr};
+            const hipError_t e = launch_entropy_set(ea, ne, s[ms[0]]->stream, tm ? &tc : nullptr, tm ? &tp : nullptr);
+            for (int q = 0; q < ne; ++q) {
+                note(t, ms[q], e == hipSuccess ? kOk : kErrHip);
+                if (e != hipSuccess) s[ms[q]] = nullptr;
+            }
+        } else {
+            for (int q = 0; q < ne; ++q) {
+                const int m = ms[q];
+                const int st = enc.launch_entropy_phase(*s[m], carry ? carry[m] : nullptr);
+                note(t, m, st);
+                if (st) s[m] = nullptr;
+            }
+        }
+        for (int q = 0; carry && q < ne; ++q)
+            if (s[ms[q]] && carry[ms[q]]) carry[ms[q]]->export_queued.store(1, std::memory_order_release);
+    }
+
+    // Drain set k: its results, and its host outputs' copies queued.  idle: work for the
+    // waits while frames' tables are pending.
+    void drain(int k, const std::function<bool()>* idle) {
+        for (int m = 0; m < members(k); ++m) {
+            Slot& s = slot(k, m);
+            if (!frame(k, m).status)
+                note(k, m, enc.finish(s, frame(k, m), flags, /*guess_wait=*/m == 0, pend.empty() ? nullptr : idle));
+            else hipStreamSynchronize(s.stream);
+        }
+    }
+};
+
+// One software pipeline on the lane's stream (steps are lane-local), in two stage
+// schedules over LaneRun's steps.
+//
+// Per-image tables.  Step i queues
+//   K1(i) [carrying set j = i-L's tables + headers to the device], K2(i),
+//   then set j's entropy kernels [the code kernel carrying set i's histograms to
+//   the host for a table worker],
+// so the host builds a set's tables while the GPU works through the L sets queued
+// ahead of its entropy launch; set i-L-D is drained D steps after that launch (about
+// D sets of queued GPU work while the host waits).  Member m of one set pairs with
+// member m of the other for the carried duties.  The pipeline's edges fall back to a
+// standalone export kernel and a table copy.
+//
+// Fixed tables: the same with L = 0 and nothing carried.  Nothing of a frame waits on the
+// host: its tables and headers are known when it is queued (fixed_tables), so step i queues
+// K1(i), K2(i) (the instance without histograms) and set i's entropy kernels back to back,
+// and drains set i-D.  There is no histogram export, no table import of another set and no
+// table build.
+int Encoder::run_lane(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* next, int set, const uint8_t qy[64],
+                      const uint8_t qc[64], uint32_t flags) {
+    LaneRun r(*this, ln, frames, total, next, set, qy, qc, flags);
+    const bool fixed = r.fixed;
+    const int L = fixed ? 0 : lookahead_, D = drain_lag_;
+    if (!fixed) r.pend.reserve((size_t)(L + D + 2) * set);
+    std::vector<Slot*>& pend = r.pend;
     const std::function<bool()> build_ready = [&]() -> bool {
         for (size_t q = 0; q < pend.size(); ++q) {
             Slot& s = *pend[q];
@@ -1477,17 +1599,11 @@ int Encoder::run_lane(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* 
         return std::chrono::duration<double, std::micro>(t - t_call).count();
     };
     // diagnostic (JPGE_CPU_PROF): this thread's CPU time per loop segment, summed per encoder
-    int64_t cpu_last = 0;
+    int64_t cpu_last = cpu_prof_ ? thread_cpu_ns() : 0;
     int64_t cpu_acc[6] = {0, 0, 0, 0, 0, 0};
-    auto thread_ns = [] {
-        timespec t;
-        clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t);
-        return (int64_t)t.tv_sec * 1000000000 + t.tv_nsec;
-    };
-    if (cpu_prof_) cpu_last = thread_ns();
     auto mark = [&](int i, int point, const Slot* job = nullptr) {
         if (cpu_prof_) {
-            const int64_t t = thread_ns();
+            const int64_t t = thread_cpu_ns();
             cpu_acc[point] += t - cpu_last;
             cpu_last = t;
         }
@@ -1496,166 +1612,59 @@ int Encoder::run_lane(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* 
                              job ? us(job->t_submit) : 0.0, job ? us(job->t_start) : 0.0,
                              job ? us(job->t_done) : 0.0});
     };
-    int n = 0;         // sets taken so far
-    bool open = true;  // the batch may still have frames
     for (int i = 0;; ++i) {
-        if (open && i == n) {  // room for a new set: take the batch's next frames
-            const int g = next->fetch_add(set, std::memory_order_relaxed);
-            if (g < total) {
-                for (int m = 0; m < set && g + m < total; ++m) mine.push_back(g + m);
-                ++n;
-            } else {
-                open = false;
-            }
-        }
-        if (!open && i >= n + L + D) break;
-        const int j = i - L, k = i - L - D;
+        r.take(i);
+        if (!r.open && i >= r.n + L + D) break;
+        const int j = i - L, k = j - D;
+        const bool have_j = j >= 0 && j < r.n;
         mark(i, 0);
-        Slot* sj[kMaxSet] = {};  // set j's members, tables built, ready for their entropy kernels
-        if (j >= 0 && j < n) {
-            for (int m = 0; m < members(j); ++m) {
-                if (frame(j, m).status) continue;
-                Slot& s = slot(j, m);
-                if (!s.tables_done.load(std::memory_order_acquire)) {
-                    s.tables_status = build_tables(s, /*parallel=*/false);
-                    s.tables_done.store(1, std::memory_order_release);
-                }
-                if (s.tables_status) note(j, m, s.tables_status);
-                else sj[m] = &s;
+        Slot* sj[kMaxSet] = {};  // per-image tables: set j's members, tables built, ready for their entropy kernels
+        Slot* si[kMaxSet] = {};  // set i's members, K1 and K2 queued
+        for (int m = 0; !fixed && have_j && m < r.members(j); ++m) {
+            if (r.frame(j, m).status) continue;
+            Slot& s = r.slot(j, m);
+            if (!s.tables_done.load(std::memory_order_acquire)) {
+                s.tables_status = build_tables(s, /*parallel=*/false);
+                s.tables_done.store(1, std::memory_order_release);
             }
-            mark(i, 1, sj[0]);
-        } else {
-            mark(i, 1);
+            if (s.tables_status) r.note(j, m, s.tables_status);
+            else sj[m] = &s;
         }
-        Slot* si[kMaxSet] = {};  // set i's members whose histograms set j's code kernels export
-        bool imported[kMaxSet] = {};
-        if (i < n) {
-            const int mi = members(i);
-            if (set == 1) {
-                Slot& s = slot(i, 0);
-                note(i, 0, phase1(s, frame(i, 0), qy, qc, flags, sj[0], /*export_hist=*/sj[0] == nullptr));
-                if (!frame(i, 0).status) {
-                    imported[0] = sj[0] != nullptr;
-                    si[0] = sj[0] ? &s : nullptr;
-                    submit_tables(s);
-                }
-            } else {
-                Slot* ss[kMaxSet];
-                FdctArgs fa[kMaxSet];
-                StatsArgs sa[kMaxSet];
-                int ms[kMaxSet], ok = 0;
-                for (int m = 0; m < mi; ++m) {
-                    Slot& s = slot(i, m);
-                    const int st = prep1(s, frame(i, m), qy, qc, flags, sj[m], fa[ok], sa[ok]);
-                    note(i, m, st);
-                    if (st) continue;
-                    ss[ok] = &s;
-                    ms[ok++] = m;
-                }
-                if (ok) {
-                    const int st = phase1_set(ss, ok, fa, sa);
-                    for (int q = 0; q < ok; ++q) {
-                        const int m = ms[q];
-                        note(i, m, st);
-                        if (st) continue;
-                        Slot& s = slot(i, m);
-                        imported[m] = sj[m] != nullptr;
-                        if (sj[m]) {
-                            si[m] = &s;
-                        } else {  // (no code kernel of set j to carry the export)
-                            const hipError_t e = launch_hist_export(s.hist, s.d_hist_host->cnt, s.d_hist_host->key,
-                                                                    &s.d_hist_host->seq, s.seq, s.stream);
-                            note(i, m, e == hipSuccess ? kOk : kErrHip);
-                            if (e == hipSuccess) s.export_queued.store(1, std::memory_order_release);
-                        }
-                        if (!frame(i, m).status) submit_tables(s);
-                    }
-                }
-            }
+        mark(i, 1, sj[0]);
+        if (i < r.n) r.queue_phase1(i, sj, /*lone_exports=*/!fixed, si);
+        for (int m = 0; !fixed && m < kMaxSet; ++m) {
+            if (!si[m]) continue;
+            // (no code kernel of set j to carry the export, and no K2 of its own did)
+            if (!sj[m] && !si[m]->export_queued.load(std::memory_order_relaxed)) r.note(i, m, export_hist(*si[m]));
+            if (!r.frame(i, m).status) submit_tables(*si[m]);
         }
         mark(i, 2);
-        if (j >= 0 && j < n) {
-            // set j's entropy kernels: one launch per kernel for the set, or frame by frame
-            // (a single frame; a member its code kernel does not place)
-            EntropyArgs ea[kMaxSet];
-            int ms[kMaxSet], ne = 0;
-            bool as_set = set > 1;
-            for (int m = 0; m < members(j); ++m) {
-                if (!sj[m]) continue;
-                const int st = imported[m] ? kOk : import_tables_copy(*sj[m]);
-                note(j, m, st);
-                if (st) {
-                    sj[m] = nullptr;
-                    continue;
-                }
-                ea[ne] = entropy_args(*sj[m]);
-                if (Slot* ex = si[m] && !frame(i, m).status ? si[m] : nullptr) {  // (carried export)
-                    ea[ne].exp_hist = ex->hist;
-                    ea[ne].exp_cnt = ex->d_hist_host->cnt;
-                    ea[ne].exp_key = ex->d_hist_host->key;
-                    ea[ne].exp_seq = &ex->d_hist_host->seq;
-                    ea[ne].exp_seqv = ex->seq;
-                }
-                as_set = as_set && ea[ne].done;
-                ms[ne++] = m;
+        if (have_j && fixed) {
+            r.queue_entropy(i, si, nullptr);  // (j == i)
+        } else if (have_j) {
+            for (int m = 0; m < kMaxSet; ++m) {  // (the tables K1(i) does not carry: by a copy)
+                if (!sj[m] || si[m]) continue;
+                const int st = import_tables_copy(*sj[m]);
+                r.note(j, m, st);
+                if (st) sj[m] = nullptr;
             }
-            if (ne) {
-                if (as_set) {
-                    Slot* tm = nullptr;  // (a sampled set's member: its events time the launches)
-                    for (int q = 0; q < ne; ++q) {
-                        sj[ms[q]]->h_result[2] = 0;
-                        if (sj[ms[q]]->timed && !tm) tm = sj[ms[q]];
-                    }
-                    const KTimer tc{tm ? tm->ev[4] : nullptr, tm ? tm->ev[5] : nullptr};
-                    const KTimer tp{tm ? tm->ev[6] : nullptr, tm ? tm->ev[7] : nullptr};
-                    const hipError_t e = launch_entropy_set(ea, ne, sj[ms[0]]->stream, tm ? &tc : nullptr,
-                                                            tm ? &tp : nullptr);
-                    for (int q = 0; q < ne; ++q) note(j, ms[q], e == hipSuccess ? kOk : kErrHip);
-                    if (e != hipSuccess) ne = 0;
-                } else {
-                    for (int q = 0; q < ne; ++q) {
-                        const int m = ms[q];
-                        const int st = launch_entropy_phase(*sj[m], si[m] && !frame(i, m).status ? si[m] : nullptr);
-                        note(j, m, st);
-                        if (st) sj[m] = nullptr;
-                    }
-                }
-                for (int q = 0; q < ne; ++q) {  // exported by member m of set j's code kernel
-                    const int m = ms[q];
-                    if (sj[m] && si[m] && !frame(i, m).status) {
-                        si[m]->export_queued.store(1, std::memory_order_release);
-                        si[m] = nullptr;
-                    }
-                }
-            }
+            r.queue_entropy(j, sj, si);
         }
         mark(i, 3);
-        for (int m = 0; m < kMaxSet; ++m) {  // (no carrier: export set i's histograms on their own)
-            Slot* s = si[m];
-            if (!s) continue;
-            const hipError_t e = launch_hist_export(s->hist, s->d_hist_host->cnt, s->d_hist_host->key,
-                                                    &s->d_hist_host->seq, s->seq, s->stream);
-            note(i, m, e == hipSuccess ? kOk : kErrHip);
-            if (e == hipSuccess) s->export_queued.store(1, std::memory_order_release);
-        }
-        if (k >= 0 && k < n) {
-            for (int m = 0; m < members(k); ++m) {
-                Slot& s = slot(k, m);
-                if (!frame(k, m).status)
-                    note(k, m, finish(s, frame(k, m), flags, /*guess_wait=*/m == 0, pend.empty() ? nullptr : &build_ready));
-                else hipStreamSynchronize(s.stream);
-            }
-        }
+        for (int m = 0; !fixed && m < kMaxSet; ++m)  // (no carrier after all: set i's histograms on their own)
+            if (si[m] && !r.frame(i, m).status && !si[m]->export_queued.load(std::memory_order_relaxed))
+                r.note(i, m, export_hist(*si[m]));
+        if (k >= 0 && k < r.n) r.drain(k, &build_ready);
         mark(i, 4);
     }
     // every output byte is in place: the stream's tail, awaited by spinning (a
     // blocking stream synchronisation adds tens of us of wake-up latency)
     JPGE_HIP(hipEventRecord(ln.done, ln.stream));
     JPGE_HIP(wait_event(ln.done));
-    mark(n + L + D, 5);  // (n: this lane's set count)
+    mark(r.n + L + D, 5);  // (n: this lane's set count)
     if (cpu_prof_) {
         for (int q = 0; q < 6; ++q) cpu_ns_[q].fetch_add(cpu_acc[q], std::memory_order_relaxed);
-        cpu_frames_.fetch_add((int64_t)mine.size(), std::memory_order_relaxed);
+        cpu_frames_.fetch_add((int64_t)r.mine.size(), std::memory_order_relaxed);
     }
     if (host_trace_file_) {
         std::lock_guard<std::mutex> g(trace_mu_);
@@ -1667,103 +1676,7 @@ int Encoder::run_lane(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* 
             std::fclose(f);
         }
     }
-    return first_err;
-}
-
-// A lane's pipeline with fixed Huffman tables.  Nothing of a frame waits on the host: its
-// tables and headers are known when it is queued (fixed_tables), so step i queues K1(i),
-// K2(i) (the instance without histograms) and set i's entropy kernels back to back, and
-// drains set i - D.  There is no histogram export, no table import of another set and no
-// table build; sets, the slot ring, the drain and the result words are run_lane's.
-int Encoder::run_lane_fixed(Lane& ln, FrameDesc* frames, int total, std::atomic<int>* next, int set,
-                            const uint8_t qy[64], const uint8_t qc[64], uint32_t flags) {
-    const int S = (int)ln.slots.size() / set;  // slot sets (add_slots: > drain lag)
-    std::vector<int> mine;  // batch indices of the frames this lane took, in its order
-    mine.reserve(total);
-    auto members = [&](int t) { return std::min(set, (int)mine.size() - t * set); };
-    auto frame = [&](int t, int m) -> FrameDesc& { return frames[mine[t * set + m]]; };
-    auto slot = [&](int t, int m) -> Slot& { return *ln.slots[(t % S) * set + m]; };
-    int first_err = kOk;
-    auto note = [&](int t, int m, int st) {
-        if (st) slot(t, m).fixed.gen = 0;  // (its tables may not have reached the device)
-        if (st && !frame(t, m).status) frame(t, m).status = st;
-        if (st && !first_err) first_err = st;
-    };
-    const int D = drain_lag_;
-    int n = 0;         // sets taken so far
-    bool open = true;  // the batch may still have frames
-    for (int i = 0;; ++i) {
-        if (open && i == n) {  // room for a new set: take the batch's next frames
-            const int g = next->fetch_add(set, std::memory_order_relaxed);
-            if (g < total) {
-                for (int m = 0; m < set && g + m < total; ++m) mine.push_back(g + m);
-                ++n;
-            } else {
-                open = false;
-            }
-        }
-        if (!open && i >= n + D) break;
-        if (i < n) {
-            Slot* ss[kMaxSet];  // the members whose K1 and K2 are queued
-            int ms[kMaxSet], ok = 0;
-            if (set == 1) {
-                Slot& s = slot(i, 0);
-                note(i, 0, phase1(s, frame(i, 0), qy, qc, flags, nullptr, /*export_hist=*/false));
-                if (!frame(i, 0).status) {
-                    ss[0] = &s;
-                    ms[ok++] = 0;
-                }
-            } else {
-                FdctArgs fa[kMaxSet];
-                StatsArgs sa[kMaxSet];
-                for (int m = 0; m < members(i); ++m) {
-                    Slot& s = slot(i, m);
-                    const int st = prep1(s, frame(i, m), qy, qc, flags, nullptr, fa[ok], sa[ok]);
-                    note(i, m, st);
-                    if (st) continue;
-                    ss[ok] = &s;
-                    ms[ok++] = m;
-                }
-                if (ok) {
-                    const int st = phase1_set(ss, ok, fa, sa);
-                    for (int q = 0; q < ok; ++q) note(i, ms[q], st);
-                    if (st) ok = 0;
-                }
-            }
-            // the same set's entropy kernels: one launch per kernel for the set, or frame by
-            // frame (a single frame; a member its code kernel does not place)
-            EntropyArgs ea[kMaxSet];
-            bool as_set = set > 1;
-            Slot* tm = nullptr;  // (a sampled set's member: its events time the launches)
-            for (int q = 0; q < ok; ++q) {
-                ea[q] = entropy_args(*ss[q]);
-                as_set = as_set && ea[q].done;
-                if (ss[q]->timed && !tm) tm = ss[q];
-            }
-            if (ok && as_set) {
-                for (int q = 0; q < ok; ++q) ss[q]->h_result[2] = 0;
-                const KTimer tc{tm ? tm->ev[4] : nullptr, tm ? tm->ev[5] : nullptr};
-                const KTimer tp{tm ? tm->ev[6] : nullptr, tm ? tm->ev[7] : nullptr};
-                const hipError_t e = launch_entropy_set(ea, ok, ss[0]->stream, tm ? &tc : nullptr, tm ? &tp : nullptr);
-                for (int q = 0; q < ok; ++q) note(i, ms[q], e == hipSuccess ? kOk : kErrHip);
-            } else {
-                for (int q = 0; q < ok; ++q) note(i, ms[q], launch_entropy_phase(*ss[q], nullptr));
-            }
-        }
-        const int k = i - D;
-        if (k >= 0 && k < n) {
-            for (int m = 0; m < members(k); ++m) {
-                Slot& s = slot(k, m);
-                if (!frame(k, m).status) note(k, m, finish(s, frame(k, m), flags, /*guess_wait=*/m == 0));
-                else hipStreamSynchronize(s.stream);
-            }
-        }
-    }
-    // every output byte is in place: the stream's tail, awaited by spinning (as run_lane)
-    JPGE_HIP(hipEventRecord(ln.done, ln.stream));
-    JPGE_HIP(wait_event(ln.done));
-    if (cpu_prof_) cpu_frames_.fetch_add((int64_t)mine.size(), std::memory_order_relaxed);
-    return first_err;
+    return r.first_err;
 }
 
 int Encoder::fdct_quant(const FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags,
@@ -1875,7 +1788,7 @@ int Encoder::stripe_stats(const int32_t seed[3], uint32_t counts[1024], uint64_t
     JPGE_HIP(launch_stats(st, s.stream));
     s.seq = ++seq_counter_;
     s.hist = st.hist;
-    JPGE_HIP(launch_hist_export(st.hist, s.d_hist_host->cnt, s.d_hist_host->key, &s.d_hist_host->seq, s.seq, s.stream));
+    if (const int e = export_hist(s)) return e;
     JPGE_HIP(hipStreamSynchronize(s.stream));
     for (int i = 0; i < 1024; ++i) {
         const uint32_t c = s.h_hist->cnt[i];
@@ -2282,8 +2195,7 @@ int Encoder::encode_planes(const double* const planes[3], uint32_t rows, uint32_
     JPGE_HIP(launch_stats(st2, st));
     s.seq = ++seq_counter_;
     s.hist = st2.hist;
-    JPGE_HIP(launch_hist_export(st2.hist, s.d_hist_host->cnt, s.d_hist_host->key, &s.d_hist_host->seq, s.seq, st));
-    s.export_queued.store(1, std::memory_order_release);
+    if (const int e = export_hist(s)) return e;
     FrameDesc f;
     f.out = out;
     f.cap = cap;

@@ -160,6 +160,7 @@ class Encoder {
   private:
     struct Slot;
     struct Lane;
+    struct LaneRun;  // a lane's state for one batch, and the pipeline's steps over it
     class TableHelper;
     Encoder() = default;
     int ensure(Slot& s, const Geometry& g, size_t in_bytes, size_t out_cap);
@@ -192,17 +193,16 @@ class Encoder {
     int launch_entropy_phase(Slot& s, Slot* exp, bool lone = false, int parts = 3);
     // idle: work the wait may do between its polls (returns whether it did any)
     int finish(Slot& s, FrameDesc& f, uint32_t flags, bool guess_wait = true, const std::function<bool()>* idle = nullptr);
+    int export_hist(Slot& s);  // its histograms to the host by a launch of their own (no kernel carries them)
+    int await_call_end(Slot& s, uint32_t flags, int st);  // encode()'s end: every output byte in place (st: its status so far)
     // one lane's software pipeline over the frames it takes from fr[0..total) through `next`
-    // (frames go in sets of `set` when set > 1: a pipeline step is a set, one launch per kernel)
+    // (frames go in sets of `set` when set > 1: a pipeline step is a set, one launch per kernel);
+    // kFlagFixedTables in `flags`: the stage schedule without the host in the middle
     int run_lane(Lane& ln, FrameDesc* fr, int total, std::atomic<int>* next, int set, const uint8_t qy[64],
                  const uint8_t qc[64], uint32_t flags);
     // ---- fixed Huffman tables (set_huffman) ----
     // encode()'s single image: K1, K2, the code and the pack kernel queued at once
     int encode_fixed(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags);
-    // run_lane's pipeline without the host in the middle: a step queues K1, K2 and the
-    // entropy kernels of the same set
-    int run_lane_fixed(Lane& ln, FrameDesc* fr, int total, std::atomic<int>* next, int set, const uint8_t qy[64],
-                       const uint8_t qc[64], uint32_t flags);
     // the fixed tables' code words and the frame's headers into the slot's staging buffer,
     // unless the slot's buffers (host and device) hold them already; fresh: they are new in
     // h_tab, and the frame's transform kernel has to carry them to the device

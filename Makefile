@@ -15,7 +15,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -I$(SR
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Wno-unused-parameter -Wno-unused-result \
             -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -I$(SRC) -Iinclude $(HIPEXTRA)
 
-HOST_SRCS := encoder.cpp capi.cpp host_io.cpp huffman.cpp jpge_image.cpp ingest.cpp host_decode.cpp coding.cpp group.cpp
+HOST_SRCS := encoder.cpp encoder_stripes.cpp encoder_planes.cpp capi.cpp host_io.cpp huffman.cpp jpge_image.cpp ingest.cpp host_decode.cpp coding.cpp group.cpp
 HOST_OBJS := $(addprefix $(BUILD)/,$(HOST_SRCS:.cpp=.o))
 DEV_SRCS  := fdct.hip fdct_bgr8.hip fdct_x4.hip fdct_planar.hip fdct_nv12.hip fdct_i420.hip fdct_yuv444.hip fdct_gray.hip stats.hip entropy.hip planes.hip concat.hip
 DEV_OBJS  := $(addprefix $(BUILD)/,$(DEV_SRCS:.hip=.o))

@@ -1,16 +1,11 @@
-#include "encoder.hpp"
+#include "encoder_impl.hpp"
 #include "host_par.hpp"
 
 #include <algorithm>
 #include <array>
-#include <atomic>
-#include <chrono>
-#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstdio>
-#include <cstring>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -20,96 +15,15 @@
 
 namespace jpge {
 
-#define JPGE_HIP(expr)                                   \
-    do {                                                 \
-        if ((expr) != hipSuccess) return kErrHip;        \
-    } while (0)
-
-namespace {
-
-// MCU shape of a subsampling mode (jpge.h JPGE_S*): Y blocks across, blocks per MCU
-// and the 4:2:0 chroma filter; false for an unknown mode.
-bool mode_shape(int mode, uint32_t& yh, uint32_t& bpm, uint32_t& cfilt) {
-    cfilt = kFiltS420m;
-    switch (mode) {
-        case 420: yh = 2; bpm = 6; return true;
-        case 4201: yh = 2; bpm = 6; cfilt = kFiltS420lm; return true;
-        case 4200: yh = 2; bpm = 6; cfilt = kFiltS420; return true;
-        case 444: yh = 1; bpm = 3; return true;
-        case 422: yh = 2; bpm = 4; return true;
-        case 411: yh = 4; bpm = 6; return true;
-        default: return false;
-    }
-}
-
-// The frame in whole MCUs (4:2:0: 16x16 px, the reference's padding, Image.cpp:480-531;
-// the other modes pad to their own MCU size: edge replication either way)
-inline Geometry geometry(uint32_t w, uint32_t h, int mode = 420) {
-    Geometry g;
-    g.width = w;
-    g.height = h;
-    mode_shape(mode, g.yh, g.bpm, g.cfilt);
-    g.mw = (w + g.mcu_w() - 1) / g.mcu_w();
-    g.mh = (h + g.mcu_h() - 1) / g.mcu_h();
-    return g;
-}
-
-// One component (kFmtGray8): the frame in single 8x8 blocks, no chroma (kernels.hpp Geometry)
-inline Geometry gray_geometry(uint32_t w, uint32_t h) {
-    Geometry g;
-    g.width = w;
-    g.height = h;
-    g.yh = 1;
-    g.bpm = 1;
-    g.mw = (w + 7) / 8;
-    g.mh = (h + 7) / 8;
-    return g;
-}
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// Host-side wait with low wake-up latency (the pipeline waits on short intervals).
-inline hipError_t wait_event(hipEvent_t e) {
+// (encoder_impl.hpp describes both waits)
+hipError_t wait_event(hipEvent_t e) {
     hipError_t r;
     while ((r = hipEventQuery(e)) == hipErrorNotReady) {
     }
     return r;
 }
-
-// Poll a sequence word a kernel writes into mapped host memory after its data
-// (release-ordered).  `nap`: sleep ~10 us between polls (pool workers, which have
-// slack) instead of spinning (the submitting thread).  Bounded: a stream error or
-// ~20 s without progress fails.  The stream is queried only after 2 ms without the
-// word (then every ms): a stream query enqueues a marker behind the newest launch,
-// which costs the GPU ~6 us of idle each time.  `queued`: set once the kernel that
-// writes the word is on the stream (another thread launches it); before that an
-// idle stream is no error.
-//
-// `guess` (napping waits): a running estimate of how long this wait takes at its call
-// site.  The first sleep covers most of it in one wake-up, and naps poll the rest, so
-// a wait of ~100 us costs two or three wake-ups instead of ten.  The sleep is shortened
-// by twice the waits' spread, so irregular waits (16384^2 frames) are polled, not slept
-// through.
-struct WaitGuess {
-    double ema_us = 0;  // smoothed wait duration (0: none yet)
-    double dev_us = 0;  // smoothed |wait - ema_us|
-    double frac = 0;    // first sleep = frac * ema - 2 * dev (0: off)
-    double first_sleep_us() const { return frac * ema_us - 2.0 * dev_us; }
-    void add(double us) {
-        if (ema_us > 0) {
-            dev_us = 0.85 * dev_us + 0.15 * std::fabs(us - ema_us);
-            ema_us = 0.85 * ema_us + 0.15 * us;
-        } else {
-            ema_us = us;
-        }
-    }
-    // statistics (JPGE_CPU_PROF): waits, waits already satisfied on entry, naps, total us
-    uint64_t waits = 0, ready = 0, naps = 0;
-    double total_us = 0;
-};
-inline int wait_seq(const uint64_t* word, uint64_t seq, hipStream_t stream, int nap_us = 0,
-                    const std::atomic<int>* queued = nullptr, WaitGuess* guess = nullptr,
-                    const std::function<bool()>* work = nullptr) {
+int wait_seq(const uint64_t* word, uint64_t seq, hipStream_t stream, int nap_us, const std::atomic<int>* queued,
+             WaitGuess* guess, const std::function<bool()>* work) {
     const bool nap = nap_us > 0;
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
@@ -172,6 +86,21 @@ inline int wait_seq(const uint64_t* word, uint64_t seq, hipStream_t stream, int 
     }
 }
 
+void read_hist(const HostHist& h, uint32_t counts[1024], uint64_t first[1024]) {
+    for (int i = 0; i < 1024; ++i) {
+        counts[i] = h.cnt[i];
+        first[i] = h.cnt[i] ? ~h.key[i] : ~0ull;
+    }
+}
+
+bool tables_nonzero(const uint8_t qy[64], const uint8_t qc[64]) {
+    for (int i = 0; i < 64; ++i)
+        if (!qy[i] || !qc[i]) return false;
+    return true;
+}
+
+namespace {
+
 // Pipeline depth limits (defaults in Encoder; the slots in flight = lookahead + drain lag + 1).
 constexpr int kMaxLookahead = 8;
 constexpr int kMaxDrainLag = 4;
@@ -198,31 +127,8 @@ int64_t thread_cpu_ns() {  // the calling thread's CPU time (JPGE_CPU_PROF)
 constexpr size_t kTabBytes = 4 * 256 * 4;  // code tables as uploaded
 constexpr size_t kHdrMax = 4096;           // headers SOI .. SOS (<= 20 + 2*69 + 19 + 4*277 + 14)
 
-// Control block, zeroed at the start of every frame by the first kernel (K1).
-struct CtlLayout {
-    size_t cnt, key, rec, done, total;  // [0, total): zeroed by K1 every frame
-    size_t place, summary, alloc;  // not zeroed (written before they are read)
-    explicit CtlLayout(uint32_t ntiles) {  // ntiles: entropy workgroups (records)
-        size_t o = 0;
-        cnt = o; o += align_up((size_t)kHistReplicas * 4 * 256 * 4, 256);
-        key = o; o += align_up(4 * 256 * 8, 256);
-        rec = o; o += align_up((size_t)ntiles * kEntropyRecordBytes, 256);
-        done = o; o += 256;
-        total = o;
-        place = o; o += align_up((size_t)ntiles * sizeof(WgPlace), 256);
-        summary = o; o += 256;
-        alloc = o;
-    }
-};
-
 constexpr size_t kStatsDoneOff = 64;  // K2's finished-workgroup count: a line of its own in the `done` block
 constexpr size_t kPackDoneOff = 128;  // the pack kernel's count, end offset and flag: another line
-
-struct HostHist {  // written by hist_export_kernel into mapped pinned memory
-    uint32_t cnt[4 * 256];  // replicas summed
-    uint64_t key[4 * 256];  // ~first-occurrence key
-    uint64_t seq;           // frame sequence number, written after the data
-};
 
 }  // namespace
 
@@ -305,95 +211,6 @@ class Encoder::TableHelper {
     bool inv_ = false;
     HuffTable* tabs_ = nullptr;
     int* ok_ = nullptr;
-};
-
-struct Encoder::Slot {
-    hipStream_t stream = nullptr;  // the encoder's stream (shared by all slots, not owned)
-    // 0-2, 4-5 kernel timing brackets (3, 6, 7 unused)
-    hipEvent_t ev[8] = {};
-    Geometry g;
-    // device workspace (capacities)
-    size_t cap_blk = 0, cap_in = 0, cap_out = 0, cap_ctl = 0;
-    uint8_t* d_in = nullptr;
-    int16_t* d_coef = nullptr;
-    uint8_t* d_ctl = nullptr;
-    uint8_t* d_ubuf = nullptr;  // unstuffed entropy-coded segment (K3 internal)
-    size_t cap_ubuf = 0;
-    uint16_t* d_recs = nullptr;    // K2's symbol records, kTileRecords per entropy tile
-    uint32_t* d_tcount = nullptr;  // records per tile
-    size_t cap_tiles = 0;          // (capacities: records, in words; tiles)
-    size_t cap_recs = 0;
-    uint8_t* d_out = nullptr;
-    uint32_t* d_tab = nullptr;  // [1024] tables, then the header bytes (one upload)
-    // pinned host staging
-    HostHist* h_hist = nullptr;
-    HostHist* d_hist_host = nullptr;  // device view of h_hist
-    uint32_t* h_tab = nullptr;     // same layout as d_tab (mapped)
-    uint32_t* d_tab_host = nullptr;  // device view of h_tab
-    uint64_t* h_result = nullptr;  // mapped: written by the entropy kernel's last workgroup
-                                   // ([0, 4)); [6]: encode()'s gate word (gate())
-    uint64_t* d_result_host = nullptr;
-    // per-frame state between phases
-    const uint8_t* in_dev = nullptr;
-    size_t in_stride = 0;
-    int in_fmt = kFmtRgb8;         // the input's layout (kernels.hpp kFmt*)
-    size_t in_plane_stride = 0;
-    uint8_t* out_dev = nullptr;
-    size_t out_cap = 0;
-    size_t hdr_len = 0;
-    uint64_t symbols = 0;              // Huffman-coded symbols (= K2 symbol records) of the frame
-    uint8_t qy[64], qc[64];
-    bool timed = false;                // this frame's kernels are bracketed by timing events
-    int timed_frames = 1;              // frames those kernels covered (a frame set's launches)
-    bool count_symbols = false;        // a member of a timed launch: its symbols go to times_.symbols
-    HistPtrs hist{};                   // this frame's device histograms (in d_ctl)
-    uint64_t seq = 0;                  // frame sequence number (handshakes via mapped memory)
-    std::atomic<int> tables_done{0};   // set by build_tables (any thread)
-    std::atomic<int> export_queued{0}; // the kernel exporting this frame's histograms is launched
-    std::chrono::steady_clock::time_point t_submit, t_start, t_done;  // table job (host trace)
-    // stripe context (a row stripe of a larger image; whole frames: zero seeds and
-    // bases, header dimensions = the frame's)
-    DcSeed seed;
-    Restart rst;  // restart intervals of the frame (stripe: its first MCU in the image's numbering)
-    uint64_t key_y0 = 0, key_c0 = 0, key_ncb = 0;
-    uint32_t img_w = 0, img_h = 0;
-    int tables_status = 0;
-    bool inline_tables = false;  // this frame's tables are built inside its lane's pipeline (its waits use the lane's guess)
-    // the lane's wait estimates (histograms when its own thread builds the tables; results)
-    WaitGuess* guess_hist = nullptr;
-    WaitGuess* guess_result = nullptr;
-    // Fixed Huffman tables: what h_tab and d_tab hold of them (gen 0: nothing; a frame with
-    // per-image tables overwrites both).  A frame whose key equals it finds its code words
-    // and headers on the device already.
-    struct FixedKey {
-        uint64_t gen = 0;  // the setting (Encoder::huff_gen_)
-        uint32_t w = 0, h = 0, restart = 0, samp = 0;  // samp: Y sampling (H << 4 | V), 0 = one component
-        uint8_t qy[64] = {}, qc[64] = {};
-        bool operator==(const FixedKey& o) const {
-            return gen == o.gen && w == o.w && h == o.h && restart == o.restart && samp == o.samp &&
-                   !std::memcmp(qy, o.qy, 64) && !std::memcmp(qc, o.qc, 64);
-        }
-    } fixed;
-
-    uint32_t* gate() const { return reinterpret_cast<uint32_t*>(h_result + 6); }
-
-    // The carried export of `e`: its code kernel takes exp's histograms (a later frame's)
-    // to the host on the way; nullptr: none.
-    static void carry_export(EntropyArgs& e, const Slot* exp) {
-        e.exp_hist = exp ? exp->hist : HistPtrs{};
-        e.exp_cnt = exp ? exp->d_hist_host->cnt : nullptr;
-        e.exp_key = exp ? exp->d_hist_host->key : nullptr;
-        e.exp_seq = exp ? &exp->d_hist_host->seq : nullptr;
-        e.exp_seqv = exp ? exp->seq : 0;
-    }
-
-    ~Slot() {
-        hipFree(d_in); hipFree(d_coef); hipFree(d_ctl); hipFree(d_ubuf);
-        hipFree(d_recs); hipFree(d_tcount);
-        hipFree(d_out); hipFree(d_tab);
-        hipHostFree(h_hist); hipHostFree(h_tab); hipHostFree(h_result);
-        for (auto& e : ev) if (e) hipEventDestroy(e);
-    }
 };
 
 // An independent pipeline: its own stream and slot ring; lanes other than 0 own a
@@ -739,47 +556,35 @@ void Encoder::dump_stamps(const Slot& s) {
     hipMemset(d_dbg_, 0, dbg_words_ * 8);
 }
 
+// A workspace buffer of at least `need` units (`bytes` for them): kept, or freed and
+// allocated anew.  After a failed allocation the pointer is null and the capacity zero.
+template <class T>
+static int grow(T*& p, size_t& cap, size_t need, size_t bytes) {
+    if (need <= cap) return kOk;
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+    JPGE_HIP(hipMalloc((void**)&p, bytes));
+    cap = need;
+    return kOk;
+}
+
 int Encoder::ensure(Slot& s, const Geometry& g, size_t in_bytes, size_t out_cap) {
     const size_t nblk = g.nblocks();
-    if (nblk > s.cap_blk) {
-        hipFree(s.d_coef);
-        s.d_coef = nullptr; s.cap_blk = 0;
-        JPGE_HIP(hipMalloc((void**)&s.d_coef, nblk * 128));
-        s.cap_blk = nblk;
-    }
+    if (const int st = grow(s.d_coef, s.cap_blk, nblk, nblk * 128)) return st;
     const CtlLayout L(layout(g).grid());
     const size_t ntiles = seg_tiles(layout(g));
-    const size_t nrecs = (size_t)seg_tiles(layout(g)) * kTileRecords;
-    if (ntiles > s.cap_tiles || nrecs > s.cap_recs) {
-        hipFree(s.d_recs); hipFree(s.d_tcount);
-        s.d_recs = nullptr; s.d_tcount = nullptr; s.cap_tiles = s.cap_recs = 0;
-        JPGE_HIP(hipMalloc((void**)&s.d_recs, nrecs * sizeof(*s.d_recs)));
-        JPGE_HIP(hipMalloc((void**)&s.d_tcount, ntiles * kRecSub * 4));
-        s.cap_tiles = ntiles;
-        s.cap_recs = nrecs;
+    const size_t nrecs = ntiles * kTileRecords;
+    if (ntiles > s.cap_tiles || nrecs > s.cap_recs) {  // (the records and their counts grow together)
+        s.cap_tiles = s.cap_recs = 0;
+        if (const int st = grow(s.d_recs, s.cap_recs, nrecs, nrecs * sizeof(*s.d_recs))) return st;
+        if (const int st = grow(s.d_tcount, s.cap_tiles, ntiles, ntiles * kRecSub * 4)) return st;
     }
     const size_t ubuf = entropy_ubuf_bytes(layout(g));
-    if (ubuf > s.cap_ubuf) {
-        hipFree(s.d_ubuf); s.d_ubuf = nullptr; s.cap_ubuf = 0;
-        JPGE_HIP(hipMalloc((void**)&s.d_ubuf, ubuf));
-        s.cap_ubuf = ubuf;
-    }
-    if (L.alloc > s.cap_ctl) {
-        hipFree(s.d_ctl); s.d_ctl = nullptr; s.cap_ctl = 0;
-        JPGE_HIP(hipMalloc((void**)&s.d_ctl, L.alloc));
-        s.cap_ctl = L.alloc;
-    }
-    if (in_bytes > s.cap_in) {
-        hipFree(s.d_in); s.d_in = nullptr; s.cap_in = 0;
-        JPGE_HIP(hipMalloc((void**)&s.d_in, in_bytes));
-        s.cap_in = in_bytes;
-    }
-    if (out_cap > s.cap_out) {
-        hipFree(s.d_out); s.d_out = nullptr; s.cap_out = 0;
-        JPGE_HIP(hipMalloc((void**)&s.d_out, out_cap));
-        s.cap_out = out_cap;
-    }
-    return kOk;
+    if (const int st = grow(s.d_ubuf, s.cap_ubuf, ubuf, ubuf)) return st;
+    if (const int st = grow(s.d_ctl, s.cap_ctl, L.alloc, L.alloc)) return st;
+    if (const int st = grow(s.d_in, s.cap_in, in_bytes, in_bytes)) return st;
+    return grow(s.d_out, s.cap_out, out_cap, out_cap);
 }
 
 SegLayout Encoder::slot_layout(const Slot& s) const {
@@ -908,21 +713,13 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     const size_t crows = chroma_dim(f.height), crow = f.fmt == kFmtNv12 ? row : chroma_dim(f.width);  // (4:2:0 layouts)
     const size_t cpitch = (size_t)fmt_chroma_pitch(f.fmt, stride), dev_cpitch = (size_t)fmt_chroma_pitch(f.fmt, dev_pitch);
     const size_t dev_bytes = half ? dev_plane + (planes - 1) * dev_cpitch * crows : planes * dev_plane;
-    const size_t in_bytes = (flags & kFlagDeviceInput) ? 0 : dev_bytes;
-    const size_t out_cap = (flags & kFlagDeviceOutput) ? 0 : max_jpeg_bytes(f.width, f.height);
-    for (int i = 0; i < 64; ++i)
-        if (!qy[i] || !qc[i]) return kErrArg;
+    const bool dev_in = (flags & kFlagDeviceInput) != 0, dev_out = (flags & kFlagDeviceOutput) != 0;
+    const size_t in_bytes = dev_in ? 0 : dev_bytes;
+    const size_t out_cap = dev_out ? 0 : max_jpeg_bytes(f.width, f.height);
+    if (!tables_nonzero(qy, qc)) return kErrArg;
     const int st0 = ensure(s, g, in_bytes, out_cap);
     if (st0) return st0;
-    std::memcpy(s.qy, qy, 64);
-    std::memcpy(s.qc, qc, 64);
-    s.g = g;
-    s.in_fmt = f.fmt;
-    if (flags & kFlagDeviceInput) {
-        s.in_dev = f.rgb;
-        s.in_stride = stride;
-        s.in_plane_stride = planes > 1 ? plane_stride : 0;
-    } else {
+    if (!dev_in) {
         // (planar: the planes one after the other, dev_pitch * height bytes each)
         if (stride == dev_pitch && (planes == 1 || plane_stride == dev_plane))
             // one linear copy (a 2D copy can fall back to a slower engine path)
@@ -939,23 +736,10 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
             for (size_t c = 0; c < planes; ++c)
                 JPGE_HIP(hipMemcpy2DAsync(s.d_in + c * dev_plane, dev_pitch, f.rgb + c * plane_stride, stride, row,
                                           f.height, hipMemcpyHostToDevice, s.stream));
-        s.in_dev = s.d_in;
-        s.in_stride = dev_pitch;
-        s.in_plane_stride = planes > 1 ? dev_plane : 0;
     }
-    if (flags & kFlagDeviceOutput) {
-        s.out_dev = f.out;
-        s.out_cap = f.cap;
-    } else {
-        s.out_dev = s.d_out;
-        s.out_cap = s.cap_out;
-    }
-    s.seed = DcSeed();
-    s.rst = Restart();
-    s.rst.mcus = restart_mcus_;
-    s.key_y0 = s.key_c0 = s.key_ncb = 0;
-    s.img_w = f.width;
-    s.img_h = f.height;
+    s.begin(g, qy, qc, dev_in ? f.rgb : s.d_in, dev_in ? stride : dev_pitch, f.fmt,
+            planes > 1 ? (dev_in ? plane_stride : dev_plane) : 0, dev_out ? f.out : s.d_out,
+            dev_out ? f.cap : s.cap_out, restart_mcus_, f.width, f.height);
     if (flags & kFlagFixedTables) {
         // fixed Huffman tables: the frame's own transform kernel carries its code words and
         // headers to the device, where they are new there
@@ -968,8 +752,6 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     a = fdct_args(s, f.maxval, imp);
     st = stats_args(s);
     st.fixed = (flags & kFlagFixedTables) ? 1u : 0u;
-    s.tables_done.store(0, std::memory_order_relaxed);
-    s.export_queued.store(0, std::memory_order_relaxed);
     return kOk;
 }
 
@@ -982,7 +764,6 @@ int Encoder::phase1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uin
     if (const int st = prep1(s, f, qy, qc, flags, imp, a, st2)) return st;
     const clk::time_point t1 = lat_prof_ ? clk::now() : clk::time_point{};
     s.timed = timing_every_ && (frame_counter_++ % (uint64_t)timing_every_) == 0;
-    s.timed_frames = 1;
     s.count_symbols = s.timed;
     // sampled frames: each kernel launched with its own events (KTimer, kernels.hpp)
     const KTimer t1k{s.ev[0], s.ev[1]}, t2k{s.ev[2], s.ev[3]};
@@ -1020,7 +801,7 @@ int Encoder::phase1_set(Slot* const* s, int n, const FdctArgs* a_in, const Stats
         if (!fdct_wgs_ && n > 1) a[m].wgs = kSetFdctWgs;
     }
     // a sampled set: its launches timed with the first member's events, as n frames' work
-    for (int m = 0; m < n; ++m) s[m]->timed = false;
+    // (the other members stay untimed, as Slot::begin left them)
     const uint64_t c = frame_counter_.fetch_add((uint64_t)n);
     Slot& t = *s[0];
     const uint64_t E = (uint64_t)timing_every_;
@@ -1208,7 +989,7 @@ int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], ui
     JPGE_HIP(hipSetDevice(device_));
     flags &= ~kFlagFixedTables;
     if (huff_mode_) return encode_fixed(f, qy, qc, flags | kFlagFixedTables);
-    Slot& s = *lanes_[0]->slots[0];
+    Slot& s = slot0();
     using clk = std::chrono::steady_clock;
     clk::time_point T[6];
     if (lat_prof_) T[0] = clk::now();
@@ -1315,7 +1096,7 @@ int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], ui
 // headers to the device where the slot does not hold them yet), and the call waits for the
 // pack kernel's result word alone: no gate kernel, no table thread, no histogram wait.
 int Encoder::encode_fixed(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags) {
-    Slot& s = *lanes_[0]->slots[0];
+    Slot& s = slot0();
     int st = phase1(s, f, qy, qc, flags, nullptr, /*export_hist=*/false);
     if (!st) st = launch_entropy_phase(s, nullptr, /*lone=*/true);
     if (st) s.fixed.gen = 0;  // (the tables may not have reached the device)
@@ -1683,7 +1464,7 @@ int Encoder::fdct_quant(const FrameDesc& f, const uint8_t qy[64], const uint8_t 
                         int16_t* y, int16_t* cb, int16_t* cr) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
-    Slot& s = *lanes_[0]->slots[0];
+    Slot& s = slot0();
     flags &= ~kFlagFixedTables;  // (the stage entries are the same in every Huffman mode)
     int st = phase1(s, f, qy, qc, flags | kFlagDeviceOutput | kFlagCoefficients, nullptr, true);
     if (st) { hipStreamSynchronize(s.stream); return st; }
@@ -1711,501 +1492,15 @@ int Encoder::symbol_stats(const FrameDesc& f, const uint8_t qy[64], const uint8_
                           uint32_t counts[1024], uint64_t first[1024]) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
-    Slot& s = *lanes_[0]->slots[0];
+    Slot& s = slot0();
     flags &= ~kFlagFixedTables;
     int st = phase1(s, f, qy, qc, flags | kFlagDeviceOutput, nullptr, true);
     if (st) { hipStreamSynchronize(s.stream); return st; }
     JPGE_HIP(hipStreamSynchronize(s.stream));
-    for (int t = 0; t < 4; ++t)
-        for (int i = 0; i < 256; ++i) {
-            const uint32_t c = s.h_hist->cnt[t * 256 + i];
-            counts[t * 256 + i] = c;
-            first[t * 256 + i] = c ? ~s.h_hist->key[t * 256 + i] : ~0ull;
-        }
+    read_hist(*s.h_hist, counts, first);
     return kOk;
 }
 
-
-// ---- stripes ----
-// A stripe is the MCU rows [mcu_row0, mcu_row0 + mcu_rows) of a width x height
-// image; its own geometry has the stripe's real pixel rows (the last stripe's bottom
-// padding replicates the image's last row, Image.cpp:511-519).  Every phase runs on
-// lane 0's first slot and returns when its results are on the host.
-int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const uint8_t qc[64], int32_t last_dc[3]) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    if (!d.rgb || !last_dc || d.width == 0 || d.height == 0 || d.width > 65535 || d.height > 65535) return kErrArg;
-    if (mode_ != 420) return kErrArg;  // stripes are S420_m (the reference's subsampling)
-    if (huff_mode_) return kErrArg;    // and share per-image tables (the histogram all-reduce)
-    if (fmt_planes(fmt_) != 1 || fmt_gray(fmt_)) return kErrArg;  // and interleaved colour (the stripe pointer is one row of pixels)
-    if (d.maxval < 1 || d.maxval > 255) return kErrRange;
-    const uint32_t mh_img = (d.height + 15) / 16;
-    if (d.mcu_rows == 0 || d.mcu_row0 >= mh_img || d.mcu_rows > mh_img - d.mcu_row0) return kErrArg;
-    const size_t row = (size_t)d.width * fmt_bpp(fmt_), stride = d.stride ? d.stride : row;
-    if (stride < row) return kErrArg;
-    for (int i = 0; i < 64; ++i)
-        if (!qy[i] || !qc[i]) return kErrArg;
-    const uint32_t hs = std::min(16 * d.mcu_rows, d.height - 16 * d.mcu_row0);
-    const Geometry g = geometry(d.width, hs);
-    // restart intervals: the stripe must start one (its bytes are then its own)
-    if (restart_mcus_ && ((uint64_t)d.mcu_row0 * g.mw) % restart_mcus_ != 0) return kErrArg;
-    Slot& s = *lanes_[0]->slots[0];
-    if (const int st = ensure(s, g, 0, 0)) return st;
-    std::memcpy(s.qy, qy, 64);
-    std::memcpy(s.qc, qc, 64);
-    s.g = g;
-    s.in_dev = d.rgb;
-    s.in_stride = stride;
-    s.in_fmt = fmt_;
-    s.in_plane_stride = 0;
-    s.img_w = d.width;
-    s.img_h = d.height;
-    s.seed = DcSeed();
-    s.rst = Restart();
-    s.rst.mcus = restart_mcus_;
-    s.rst.mcu0 = d.mcu_row0 * g.mw;
-    s.key_y0 = 2ull * d.mcu_row0 * (2ull * g.mw);  // Y blocks above the stripe (raster)
-    s.key_c0 = (uint64_t)d.mcu_row0 * g.mw;         // Cb blocks above it
-    s.key_ncb = (uint64_t)mh_img * g.mw;            // Cb blocks of the image
-    JPGE_HIP(launch_fdct(fdct_args(s, d.maxval, nullptr), s.stream));
-    int16_t lastmcu[6 * 64];  // the stripe's last MCU: its Y11, Cb and Cr DCs seed the next stripe
-    JPGE_HIP(hipMemcpyAsync(lastmcu, s.d_coef + ((size_t)g.nmcu() - 1) * 384, sizeof lastmcu, hipMemcpyDeviceToHost,
-                            s.stream));
-    JPGE_HIP(hipStreamSynchronize(s.stream));
-    last_dc[0] = lastmcu[3 * 64];
-    last_dc[1] = lastmcu[4 * 64];
-    last_dc[2] = lastmcu[5 * 64];
-    return kOk;
-}
-
-int Encoder::stripe_stats(const int32_t seed[3], uint32_t counts[1024], uint64_t first[1024]) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    Slot& s = *lanes_[0]->slots[0];
-    if (!s.in_dev || !seed || !counts || !first || huff_mode_) return kErrArg;
-    for (int c = 0; c < 3; ++c) s.seed.v[c] = seed[c];
-    const StatsArgs st = stats_args(s);
-    JPGE_HIP(launch_stats(st, s.stream));
-    s.seq = ++seq_counter_;
-    s.hist = st.hist;
-    if (const int e = export_hist(s)) return e;
-    JPGE_HIP(hipStreamSynchronize(s.stream));
-    for (int i = 0; i < 1024; ++i) {
-        const uint32_t c = s.h_hist->cnt[i];
-        counts[i] = c;
-        first[i] = c ? ~s.h_hist->key[i] : ~0ull;
-    }
-    return kOk;
-}
-
-int Encoder::stripe_code(const uint32_t counts[1024], const uint64_t first[1024], StripeSummary* sum,
-                         size_t* hdr_len) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    Slot& s = *lanes_[0]->slots[0];
-    if (!s.in_dev || !counts || !first || !sum || huff_mode_) return kErrArg;
-    s.out_dev = nullptr;
-    s.out_cap = 0;
-    if (const int st = build_tables_from(s, counts, first, true)) return st;
-    if (const int st = import_tables_copy(s)) return st;
-    EntropyArgs e = entropy_args(s);
-    e.done = nullptr;  // (stripes: placed by the stripe phases)
-    JPGE_HIP(launch_entropy_code_summary(e, s.stream));
-    JPGE_HIP(hipMemcpyAsync(sum, e.summary, sizeof(StripeSummary), hipMemcpyDeviceToHost, s.stream));
-    JPGE_HIP(hipStreamSynchronize(s.stream));
-    if (hdr_len) *hdr_len = s.hdr_len;
-    return kOk;
-}
-
-namespace {
-uint32_t split_bits(uint32_t ptail, uint32_t head, uint32_t b) {  // 0 < b < 8 (entropy.hip)
-    return (((ptail & ((1u << b) - 1)) << (8 - b)) | ((head & 0xFF) >> b)) & 0xFF;
-}
-uint32_t fill_bits(uint32_t eb, uint32_t tail) {  // Bitstream::fill, BitstreamGeneric.hpp:243-248
-    return (((tail & ((1u << eb) - 1)) << (8 - eb)) | (0xFFu >> eb)) & 0xFF;
-}
-}  // namespace
-
-int Encoder::stripe_place(const StripeSummary* all, int n, int index, size_t hdr_len, uint64_t* p_ext,
-                          uint64_t* q_ext, uint32_t* head_split, size_t* seg_off, size_t* total_len) {
-    if (!all || n <= 0 || index < 0 || index >= n) return kErrArg;
-    if (all[0].restart) {  // restart stripes: self-contained byte runs, one after another
-        uint64_t base = 0;
-        for (int r = 0; r < n; ++r) {
-            if (!all[r].restart) return kErrArg;
-            if (r == index) {
-                if (p_ext) *p_ext = 0;
-                if (q_ext) *q_ext = base;  // (the byte base of the stripe after the header)
-                if (head_split) *head_split = 0;
-                if (seg_off) *seg_off = r == 0 ? 0 : hdr_len + (size_t)base;
-            }
-            base += all[r].bits;
-        }
-        if (total_len) *total_len = hdr_len + (size_t)base + 2;
-        return kOk;
-    }
-    uint64_t p = 0, q = 0;
-    for (int r = 0; r < n; ++r) {
-        if (all[r].bits < 8) return kErrArg;  // (a stripe codes >= 2 bits per block, 6 blocks per MCU)
-        const uint32_t b = (uint32_t)(p & 7);
-        const uint32_t split = (b && r > 0) ? split_bits(all[r - 1].tail, all[r].head, b) : 0u;
-        if (r == index) {
-            if (p_ext) *p_ext = p;
-            if (q_ext) *q_ext = q;
-            if (head_split) *head_split = split;
-            if (seg_off) *seg_off = r == 0 ? 0 : hdr_len + (size_t)(p >> 3) + (size_t)q;
-        }
-        // 0xFF bytes stripe r owns: its inside bytes at its alignment, the byte it
-        // shares with its predecessor, the image's 1-filled final byte
-        q += all[r].ff[b] + ((b && r > 0 && split == 0xFF) ? 1u : 0u);
-        p += all[r].bits;
-        if (r == n - 1 && (p & 7) && fill_bits((uint32_t)(p & 7), all[r].tail) == 0xFF) q += 1;
-    }
-    if (total_len) *total_len = hdr_len + (size_t)((p + 7) >> 3) + (size_t)q + 2;
-    return kOk;
-}
-
-int Encoder::stripe_pack(const StripeSummary* all, int n, int index, uint8_t* out_dev, size_t cap, size_t* seg_off,
-                         size_t* seg_len, size_t* total_len) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    Slot& s = *lanes_[0]->slots[0];
-    if (!s.in_dev || !out_dev || !s.hdr_len || huff_mode_) return kErrArg;
-    uint64_t p_ext = 0, q_ext = 0;
-    uint32_t head = 0;
-    size_t off = 0, total = 0;
-    if (const int st = stripe_place(all, n, index, s.hdr_len, &p_ext, &q_ext, &head, &off, &total)) return st;
-    if (total > cap) return kErrNoSpace;
-    s.out_dev = out_dev;
-    s.out_cap = cap;
-    s.seq = ++seq_counter_;
-    s.h_result[2] = 0;
-    EntropyArgs e = entropy_args(s);
-    e.done = nullptr;  // (stripes: placed by the stripe phases)
-    if (s.rst.mcus) {
-        e.out_base = q_ext;  // (placed in phase 3, relative to the stripe's start)
-    } else {
-        e.p_ext = p_ext;
-        e.q_ext = q_ext;
-        e.head_split = head;
-    }
-    e.flags = (index == 0 ? kStripeFirst : 0u) | (index == n - 1 ? kStripeLast : 0u) | kExtPlace;
-    JPGE_HIP(launch_entropy_place_pack(e, s.stream));
-    if (const int w = wait_seq(&s.h_result[3], s.seq, s.stream)) return w;
-    JPGE_HIP(hipStreamSynchronize(s.stream));
-    if (s.h_result[1] & 4) return kErrNoSpace;
-    const size_t end = (size_t)s.h_result[0];
-    if (seg_off) *seg_off = off;
-    if (seg_len) *seg_len = end - off;
-    if (total_len) *total_len = total;
-    return (index == n - 1 && end != total) ? kErrInternal : kOk;
-}
-
-// ---- plane stages (the facade's Image stage methods; planes.hip) ----
-
-void* Encoder::scratch(int i, size_t bytes) {
-    if ((int)scratch_.size() <= i) scratch_.resize(i + 1, {nullptr, 0});
-    auto& b = scratch_[i];
-    if (b.second < bytes) {
-        hipFree(b.first);
-        b = {nullptr, 0};
-        if (hipMalloc(&b.first, bytes) != hipSuccess) return nullptr;
-        b.second = bytes;
-    }
-    return b.first;
-}
-
-#define JPGE_SCRATCH(var, idx, bytes)                     \
-    void* var = scratch((idx), (bytes));                  \
-    if (!var) return kErrHip
-
-int Encoder::stage_color(const double* const in[3], double* const out[3], size_t n, int to_ycc, uint32_t flags) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    for (int c = 0; c < 3; ++c)
-        if (!in[c] || !out[c]) return kErrArg;
-    if (n == 0) return kOk;
-    hipStream_t st = lanes_[0]->stream;
-    const size_t bytes = n * 8;
-    PlaneColorArgs a;
-    const double* din[3];
-    double* dout[3];
-    for (int c = 0; c < 3; ++c) {
-        if (flags & kFlagDeviceInput) {
-            din[c] = in[c];
-        } else {
-            JPGE_SCRATCH(b, c, bytes);
-            JPGE_HIP(hipMemcpyAsync(b, in[c], bytes, hipMemcpyHostToDevice, st));
-            din[c] = static_cast<const double*>(b);
-        }
-        if (flags & kFlagDeviceOutput) {
-            dout[c] = out[c];
-        } else {
-            JPGE_SCRATCH(b, 3 + c, bytes);
-            dout[c] = static_cast<double*>(b);
-        }
-    }
-    a.in0 = din[0]; a.in1 = din[1]; a.in2 = din[2];
-    a.out0 = dout[0]; a.out1 = dout[1]; a.out2 = dout[2];
-    a.n = n;
-    a.to_ycc = to_ycc;
-    JPGE_HIP(launch_plane_color(a, st));
-    if (!(flags & kFlagDeviceOutput))
-        for (int c = 0; c < 3; ++c) JPGE_HIP(hipMemcpyAsync(out[c], dout[c], bytes, hipMemcpyDeviceToHost, st));
-    JPGE_HIP(hipStreamSynchronize(st));
-    return kOk;
-}
-
-// applySubsampling's masks (Image.cpp:256-309) as PlaneSubsampleArgs; S444 leaves
-// the plane as it is.
-static bool subsample_mask(int mode, PlaneSubsampleArgs& a, uint32_t& vdiv) {
-    a.mask[0] = 1; a.mask[1] = 0; a.mask[2] = 0; a.mask[3] = 0;
-    a.m = 2; a.row_step = 2; a.avg_div = 0; vdiv = 2;
-    switch (mode) {
-        case 444: a.m = 1; a.row_step = 1; vdiv = 1; return true;
-        case 422: a.row_step = 1; vdiv = 1; return true;               // {1, 0}
-        case 411: a.m = 4; a.row_step = 1; vdiv = 1; return true;      // {1, 0, 0, 0}
-        case 4200: return true;                                         // {1, 0}, scanline jump
-        case 420: a.mask[1] = 1; a.avg_div = 4; return true;           // {1, 1}, averaging / 4
-        case 4201: a.avg_div = 2; return true;                         // {1, 0}, averaging / 2
-        default: return false;
-    }
-}
-
-int Encoder::subsample_shape(int mode, uint32_t rows, uint32_t cols, uint32_t* out_rows, uint32_t* out_cols) {
-    PlaneSubsampleArgs a;
-    uint32_t vdiv;
-    if (!subsample_mask(mode, a, vdiv)) return kErrArg;
-    // the reference's loop reads whole mask runs and, in pairs, the next scanline
-    if (rows == 0 || cols == 0 || cols % a.m || (a.row_step == 2 && rows % 2)) return kErrArg;
-    if (out_rows) *out_rows = rows / vdiv;
-    if (out_cols) *out_cols = cols / a.m;
-    return kOk;
-}
-
-int Encoder::stage_subsample(const double* in, uint32_t rows, uint32_t cols, int mode, double* out, uint32_t flags) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    PlaneSubsampleArgs a;
-    uint32_t vdiv, orows, ocols;
-    if (!in || !out || !subsample_mask(mode, a, vdiv)) return kErrArg;
-    if (const int e = subsample_shape(mode, rows, cols, &orows, &ocols)) return e;
-    hipStream_t st = lanes_[0]->stream;
-    const size_t ib = (size_t)rows * cols * 8, ob = (size_t)orows * ocols * 8;
-    const double* din = in;
-    if (!(flags & kFlagDeviceInput)) {
-        JPGE_SCRATCH(b, 0, ib);
-        JPGE_HIP(hipMemcpyAsync(b, in, ib, hipMemcpyHostToDevice, st));
-        din = static_cast<const double*>(b);
-    }
-    double* dout = out;
-    if (!(flags & kFlagDeviceOutput)) {
-        JPGE_SCRATCH(b, 1, ob);
-        dout = static_cast<double*>(b);
-    }
-    if (mode == 444) {
-        JPGE_HIP(hipMemcpyAsync(dout, din, ib, hipMemcpyDeviceToDevice, st));
-    } else {
-        a.in = din;
-        a.out = dout;
-        a.cols = cols;
-        a.out_rows = orows;
-        a.out_cols = ocols;
-        JPGE_HIP(launch_plane_subsample(a, st));
-    }
-    if (!(flags & kFlagDeviceOutput)) JPGE_HIP(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
-    JPGE_HIP(hipStreamSynchronize(st));
-    return kOk;
-}
-
-// Dct.hpp:220-235: A(k, n) = C0(k) sqrt(2/8) cos((2n+1) (k pi / 16)), glibc cos on the host
-static void dct_matrix_a(double A[64]) {
-    const double pi = 0x1.921fb54442d18p+1, root_two = 0x1.6a09e667f3bcdp+0;
-    const double scale = std::sqrt(2. / 8);
-    for (int k = 0; k < 8; ++k)
-        for (int n = 0; n < 8; ++n) {
-            const double cos_term = (2. * n + 1.) * ((k * pi) / (2. * 8));
-            A[k * 8 + n] = (k == 0 ? 1. / root_two : 1.) * scale * std::cos(cos_term);
-        }
-}
-
-int Encoder::stage_dct(const double* in, uint32_t rows, uint32_t cols, int dct_mode, double* out, uint32_t flags) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    if (!in || !out || rows % 8 || cols % 8 || dct_mode < kDctSimple || dct_mode > kDctArai) return kErrArg;
-    if (rows == 0 || cols == 0) return kOk;
-    hipStream_t st = lanes_[0]->stream;
-    const size_t bytes = (size_t)rows * cols * 8;
-    const double* din = in;
-    if (!(flags & kFlagDeviceInput)) {
-        JPGE_SCRATCH(b, 0, bytes);
-        JPGE_HIP(hipMemcpyAsync(b, in, bytes, hipMemcpyHostToDevice, st));
-        din = static_cast<const double*>(b);
-    }
-    double* dout = out;
-    if (!(flags & kFlagDeviceOutput)) {
-        JPGE_SCRATCH(b, 1, bytes);
-        dout = static_cast<double*>(b);
-    }
-    PlaneBlockArgs a{};
-    a.in0 = din;
-    a.cols = cols;
-    a.nblocks = (uint64_t)(rows / 8) * (cols / 8);
-    a.sink = kSinkDouble;
-    dct_matrix_a(a.A);
-    a.out_d = dout;
-    JPGE_HIP(launch_plane_block(a, dct_mode, st));
-    if (!(flags & kFlagDeviceOutput)) JPGE_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
-    JPGE_HIP(hipStreamSynchronize(st));
-    return kOk;
-}
-
-int Encoder::stage_quantize(const double* in, uint32_t rows, uint32_t cols, const uint8_t table[64], int32_t* out,
-                            uint32_t flags) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    if (!in || !out || !table || rows % 8 || cols % 8) return kErrArg;
-    if (rows == 0 || cols == 0) return kOk;
-    hipStream_t st = lanes_[0]->stream;
-    const size_t n = (size_t)rows * cols;
-    const double* din = in;
-    if (!(flags & kFlagDeviceInput)) {
-        JPGE_SCRATCH(b, 0, n * 8);
-        JPGE_HIP(hipMemcpyAsync(b, in, n * 8, hipMemcpyHostToDevice, st));
-        din = static_cast<const double*>(b);
-    }
-    int32_t* dout = out;
-    if (!(flags & kFlagDeviceOutput)) {
-        JPGE_SCRATCH(b, 1, n * 4);
-        dout = static_cast<int32_t*>(b);
-    }
-    PlaneQuantArgs a;
-    a.in = din;
-    a.out = dout;
-    a.rows = rows;
-    a.cols = cols;
-    for (int i = 0; i < 64; ++i) a.q[i] = table[i];
-    JPGE_HIP(launch_plane_quant(a, st));
-    if (!(flags & kFlagDeviceOutput)) JPGE_HIP(hipMemcpyAsync(out, dout, n * 4, hipMemcpyDeviceToHost, st));
-    JPGE_HIP(hipStreamSynchronize(st));
-    return kOk;
-}
-
-int Encoder::encode_planes(const double* const planes[3], uint32_t rows, uint32_t cols, int ycc, uint32_t real_w,
-                           uint32_t real_h, const uint8_t qy[64], const uint8_t qc[64], uint8_t* out, size_t cap,
-                           size_t* len, uint32_t flags) {
-    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
-    JPGE_HIP(hipSetDevice(device_));
-    for (int c = 0; c < 3; ++c)
-        if (!planes[c]) return kErrArg;
-    if (huff_mode_) return kErrArg;  // (writeJPEG's per-image tables only)
-    if (!out || !len || !qy || !qc || rows == 0 || cols == 0 || rows % 16 || cols % 16 || rows > 65536 ||
-        cols > 65536 || real_w == 0 || real_h == 0 || real_w > 65535 || real_h > 65535)
-        return kErrArg;
-    for (int i = 0; i < 64; ++i)
-        if (!qy[i] || !qc[i]) return kErrArg;
-    Slot& s = *lanes_[0]->slots[0];
-    hipStream_t st = s.stream;
-    // the frame as writeJPEG sees it: S420_m MCUs over the planes (rows, cols already
-    // whole MCUs: loadPPM pads to 16, Image.cpp:480-531); SOF0 carries the real size
-    Geometry g = geometry(cols, rows, 420);
-    const size_t out_cap = (flags & kFlagDeviceOutput) ? 0 : max_jpeg_bytes(cols, rows);
-    if (const int e = ensure(s, g, 0, out_cap)) return e;
-    const size_t n = (size_t)rows * cols, bytes = n * 8;
-    const double* p[3];
-    for (int c = 0; c < 3; ++c) {
-        if (flags & kFlagDeviceInput) {
-            p[c] = planes[c];
-        } else {
-            JPGE_SCRATCH(b, c, bytes);
-            JPGE_HIP(hipMemcpyAsync(b, planes[c], bytes, hipMemcpyHostToDevice, st));
-            p[c] = static_cast<const double*>(b);
-        }
-    }
-    if (!ycc) {  // *this = convertToColorSpace(YCbCr), Image.cpp:839
-        double* q[3];
-        for (int c = 0; c < 3; ++c) {
-            JPGE_SCRATCH(b, 3 + c, bytes);
-            q[c] = static_cast<double*>(b);
-        }
-        PlaneColorArgs a;
-        a.in0 = p[0]; a.in1 = p[1]; a.in2 = p[2];
-        a.out0 = q[0]; a.out1 = q[1]; a.out2 = q[2];
-        a.n = n;
-        a.to_ycc = 1;
-        JPGE_HIP(launch_plane_color(a, st));
-        for (int c = 0; c < 3; ++c) p[c] = q[c];
-    }
-    // applySubsampling(S420_m), Image.cpp:842 (Cr, then Cb: independent planes)
-    const double* sub[2];
-    for (int c = 0; c < 2; ++c) {
-        PlaneSubsampleArgs a;
-        uint32_t vdiv;
-        subsample_mask(420, a, vdiv);
-        JPGE_SCRATCH(b, 6 + c, bytes / 4);
-        a.in = p[1 + c];
-        a.out = static_cast<double*>(b);
-        a.cols = cols;
-        a.out_rows = rows / 2;
-        a.out_cols = cols / 2;
-        JPGE_HIP(launch_plane_subsample(a, st));
-        sub[c] = a.out;
-    }
-    std::memcpy(s.qy, qy, 64);
-    std::memcpy(s.qc, qc, 64);
-    s.g = g;
-    s.in_dev = reinterpret_cast<const uint8_t*>(p[0]);  // (marks the slot in use; K1 is not run)
-    s.in_stride = 0;
-    if (flags & kFlagDeviceOutput) {
-        s.out_dev = out;
-        s.out_cap = cap;
-    } else {
-        s.out_dev = s.d_out;
-        s.out_cap = s.cap_out;
-    }
-    s.seed = DcSeed();
-    s.rst = Restart();
-    s.rst.mcus = restart_mcus_;
-    s.key_y0 = s.key_c0 = s.key_ncb = 0;
-    s.img_w = real_w;
-    s.img_h = real_h;
-    s.timed = false;
-    s.count_symbols = false;
-    s.tables_done.store(0, std::memory_order_relaxed);
-    s.export_queued.store(0, std::memory_order_relaxed);
-    // applyDCT(Arai) + applyQuantization (Image.cpp:844-871) into the MCU layout; the
-    // control block is zeroed here (K1 does it on the RGB8 path)
-    const CtlLayout L(layout(g).grid());
-    JPGE_HIP(hipMemsetAsync(s.d_ctl, 0, L.total, st));
-    PlaneBlockArgs b{};
-    b.in0 = p[0];
-    b.in1 = sub[0];
-    b.in2 = sub[1];
-    b.cols = cols;
-    b.nblocks = (uint64_t)g.nblocks();
-    b.mcu = 1;
-    b.sink = kSinkMcu16;
-    for (int i = 0; i < 64; ++i) {
-        b.q[i] = qy[i];
-        b.q[64 + i] = qc[i];
-    }
-    b.out_h = s.d_coef;
-    JPGE_HIP(launch_plane_block(b, kDctArai, st));
-    const StatsArgs st2 = stats_args(s);
-    JPGE_HIP(launch_stats(st2, st));
-    s.seq = ++seq_counter_;
-    s.hist = st2.hist;
-    if (const int e = export_hist(s)) return e;
-    FrameDesc f;
-    f.out = out;
-    f.cap = cap;
-    int e = build_tables(s, false);
-    if (!e) e = import_tables_copy(s);
-    if (!e) e = launch_entropy_phase(s, nullptr);
-    if (!e) e = finish(s, f, flags);
-    hipStreamSynchronize(st);
-    *len = f.len;
-    return e;
-}
+Encoder::Slot& Encoder::slot0() { return *lanes_[0]->slots[0]; }
 
 }  // namespace jpge

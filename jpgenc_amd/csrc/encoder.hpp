@@ -162,7 +162,9 @@ class Encoder {
     struct Lane;
     struct LaneRun;  // a lane's state for one batch, and the pipeline's steps over it
     class TableHelper;
+    struct Staging;  // the plane stages' host or device buffers (encoder_planes.cpp)
     Encoder() = default;
+    Slot& slot0();   // lane 0's first slot: the single-frame calls, the stripe phases and encode_planes run on it
     int ensure(Slot& s, const Geometry& g, size_t in_bytes, size_t out_cap);
     // phase 1 (GPU): upload, transform + statistics kernels, histogram download
     // (carries `imp`'s tables to the device; exports its own histograms if asked)
@@ -187,6 +189,7 @@ class Encoder {
     FdctArgs fdct_args(Slot& s, int maxval, Slot* imp);
     StatsArgs stats_args(Slot& s);
     EntropyArgs entropy_args(Slot& s);
+    EntropyArgs stripe_entropy_args(Slot& s);  // (a stripe's: placed by the stripe phases, not by its code kernel)
     // phase 2b (GPU): table upload (when not carried) + entropy kernels
     int import_tables_copy(Slot& s);
     // lone: encode()'s single image; parts: 1 the code kernel, 2 the pack kernel, 3 both

@@ -156,6 +156,28 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
 #define JPGE_FMT_NV12 16
 #define JPGE_FMT_I420 17
 #define JPGE_FMT_YUV444_PLANAR 18
+/* 4:2:2 frames of the same samples (capture cards and webcams, SDI paths, 4:2:2 decoders):
+ * one Cb and one Cr sample per horizontal pixel pair of every row.  maxval must be 255.
+ * With cw = ceil(width / 2); `rgb` points at the frame's first byte (NV16, I422: the Y plane):
+ *   YUYV: one plane, `height` rows of cw 4-byte groups Y0 Cb Y1 Cr: pixel x has Y at byte
+ *     2x, Cb at 4(x>>1)+1, Cr at 4(x>>1)+3 of its row; stride 0 = 4 * cw; plane_stride 0.
+ *   UYVY: the same with groups Cb Y0 Cr Y1: Y at 2x+1, Cb at 4(x>>1), Cr at 4(x>>1)+2.
+ *   NV16: the Y plane, then at rgb + plane_stride (0 = stride * height) a Cb,Cr plane of
+ *     `height` rows of pitch `stride`, Cb at even bytes; stride 0 = width rounded up to even.
+ *   I422: the Y plane, then at rgb + plane_stride (0 = stride * height) the Cb plane, `height`
+ *     rows of pitch cs = (stride + 1) / 2; the Cr plane at Cb + cs * height; stride 0 = width.
+ * Such a frame is, byte for byte of the .jpg, the JPGE_FMT_YUV444_PLANAR frame whose chroma
+ * planes hold c[y][x >> 1] at pixel (y, x): in every subsampling mode (none is refused;
+ * JPGE_S422 is the native one: it keeps each cell's sample and runs no filter), with every
+ * jpge_set_yuv_transform setting (per pixel, then the mode's filter), Huffman mode and
+ * restart interval.  So the chroma is edge-replicated in the chroma domain.  With an odd
+ * width the last group's second Y byte is storage only: its value never reaches the output.
+ * The fast path needs base, stride and plane_stride 16-byte aligned (I422: a stride that is
+ * a multiple of 32); anything else works, slower. */
+#define JPGE_FMT_YUYV 20
+#define JPGE_FMT_UYVY 21
+#define JPGE_FMT_NV16 22
+#define JPGE_FMT_I422 23
 /* One plane of 8-bit luminance: `height` rows of `stride` bytes (0 = width), one byte per
  * pixel; a sample v enters the transform as the value v - 128, as a Y sample above.
  * maxval must be 255 and plane_stride 0 (else JPGE_E_ARG).  The output is a baseline JPEG
@@ -173,7 +195,7 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * jpge_fdct_quant and jpge_symbol_stats calls (their `rgb` then points at a frame in
  * that layout), also on a group member's context (jpge_group_context), and so for
  * jpge_group_encode_batch.  plane_stride: the planar layouts' bytes between planes
- * (NV12, I420: from the Y plane to the chroma), 0 = stride * height of each frame
+ * (NV12, I420, NV16, I422: from the Y plane to the chroma), 0 = stride * height of each frame
  * (contiguous CHW); non-zero with an interleaved layout, or an unknown layout: JPGE_E_ARG.  A frame's stride of 0 means width * the
  * layout's bytes per pixel (planar: width); a smaller stride is JPGE_E_ARG.  maxval
  * scales the three colour channels as before.  The fast path needs the pointer, the
@@ -181,8 +203,8 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
  * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
  * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
- * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR) and for JPGE_FMT_GRAY8 (stripes
- * are three-component 4:2:0); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
+ * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts and for
+ * JPGE_FMT_GRAY8 (stripes are three-component 4:2:0 of interleaved colour); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
 int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
 /* the current setting (plane_stride may be NULL) */
 int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride);

@@ -30,6 +30,11 @@ JPGE_FMT_RGB8, JPGE_FMT_BGR8, JPGE_FMT_RGBA8, JPGE_FMT_BGRA8, JPGE_FMT_RGB8_PLAN
 #: host frames from pack_yuv420), and planar (3, H, W)
 JPGE_FMT_NV12, JPGE_FMT_I420, JPGE_FMT_YUV444_PLANAR = 16, 17, 18
 _FMT_420 = (JPGE_FMT_NV12, JPGE_FMT_I420)
+#: 4:2:2 frames of the same samples (one Cb, Cr per horizontal pixel pair of every row): packed
+#: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 groups, NV16 (Y plane + Cb,Cr rows), I422 (three planes); host
+#: frames from pack_yuv422
+JPGE_FMT_YUYV, JPGE_FMT_UYVY, JPGE_FMT_NV16, JPGE_FMT_I422 = 20, 21, 22, 23
+_FMT_422 = (JPGE_FMT_YUYV, JPGE_FMT_UYVY, JPGE_FMT_NV16, JPGE_FMT_I422)
 #: one (H, W) plane of 8-bit luminance -> a one-component (grayscale) JPEG; no chroma: the
 #: chroma table and the subsampling mode do not enter
 JPGE_FMT_GRAY8 = 8
@@ -546,10 +551,67 @@ def pack_yuv420(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     return f, w, h, stride
 
 
+class Yuv422Frame(Yuv420Frame):
+    """A host YUYV, UYVY, NV16 or I422 frame (pack_yuv422): the layout's bytes, planes back to
+    back (plane stride 0), with the geometry that a flat buffer does not show."""
+
+
+def yuv422_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of a YUYV, UYVY, NV16 or I422 frame with plane stride 0 (stride 0: the least one)."""
+    cw = (w + 1) // 2
+    if fmt in (JPGE_FMT_YUYV, JPGE_FMT_UYVY):
+        return (stride or 4 * cw) * h
+    if fmt == JPGE_FMT_NV16:
+        return (stride or 2 * cw) * 2 * h
+    if fmt == JPGE_FMT_I422:
+        stride = stride or w
+        return stride * h + 2 * ((stride + 1) // 2) * h
+    raise ValueError(f"input layout {fmt} is not a 4:2:2 one")
+
+
+def pack_yuv422(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
+    """(frame, w, h, stride): the (H, W) Y plane and the (H, ceil(W/2)) Cb and Cr planes as one
+    contiguous host frame in layout JPGE_FMT_YUYV, _UYVY, _NV16 or _I422 with the least stride
+    and plane stride 0 (jpge.h).  The frame (a Yuv422Frame) is what encode, encode_batch,
+    fdct_quant and symbol_stats take when the input layout is `fmt`.  (Odd width: the last
+    group's second Y byte, and NV16's pad byte per Y row, are 0.)"""
+    y, cb, cr = (np.ascontiguousarray(p, np.uint8) for p in (y, cb, cr))
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
+    h, w = y.shape
+    cw = (w + 1) // 2
+    if cb.shape != (h, cw) or cr.shape != (h, cw):
+        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({h}, {cw}) for a {w}x{h} frame")
+    if fmt in (JPGE_FMT_YUYV, JPGE_FMT_UYVY):
+        stride = 4 * cw
+        y2 = np.zeros((h, 2 * cw), np.uint8)
+        y2[:, :w] = y
+        buf = np.zeros((h, cw, 4), np.uint8)
+        yo, co = (0, 1) if fmt == JPGE_FMT_YUYV else (1, 0)
+        buf[:, :, yo], buf[:, :, yo + 2] = y2[:, 0::2], y2[:, 1::2]
+        buf[:, :, co], buf[:, :, co + 2] = cb, cr
+        buf = buf.reshape(-1)
+    elif fmt == JPGE_FMT_NV16:
+        stride = 2 * cw
+        buf = np.zeros((2 * h, stride), np.uint8)
+        buf[:h, :w] = y
+        buf[h:, 0::2] = cb
+        buf[h:, 1::2] = cr
+        buf = buf.reshape(-1)
+    elif fmt == JPGE_FMT_I422:
+        stride = w  # chroma pitch (w + 1) / 2 = cw
+        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
+    else:
+        raise ValueError(f"input layout {fmt} is not a 4:2:2 one")
+    f = buf.view(Yuv422Frame)
+    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
+    return f, w, h, stride
+
+
 def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     """(width, height, row stride in bytes) of a C-contiguous frame shaped for layout `fmt`:
     (H, W, 3), (H, W, 4) or (3, H, W); GRAY8: (H, W); NV12 and I420: a pack_yuv420 frame of
-    that layout."""
+    that layout; YUYV, UYVY, NV16 and I422: a pack_yuv422 frame of that layout."""
     bpp, planes = input_format_info(fmt)
     if fmt == JPGE_FMT_GRAY8:
         if a.ndim != 2 or a.dtype != np.uint8 or a.size == 0:
@@ -560,6 +622,11 @@ def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
                 a.size != yuv420_bytes(fmt, a.width, a.height, a.stride):
             raise ValueError(f"input layout {fmt} takes a pack_yuv420({fmt}, y, cb, cr) frame")
+        return a.width, a.height, a.stride
+    if fmt in _FMT_422:
+        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
+                a.size != yuv422_bytes(fmt, a.width, a.height, a.stride):
+            raise ValueError(f"input layout {fmt} takes a pack_yuv422({fmt}, y, cb, cr) frame")
         return a.width, a.height, a.stride
     want = "(3, H, W)" if planes == 3 else f"(H, W, {bpp})"
     if a.ndim != 3 or (a.shape[0] != 3 if planes == 3 else a.shape[2] != bpp):
@@ -572,7 +639,7 @@ def _as_frame(a, fmt: int):
     """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
     if fmt == JPGE_FMT_GRAY8:
         a = np.ascontiguousarray(a)  # (the type is checked, not converted: a float plane is no gray frame)
-    elif fmt not in _FMT_420:
+    elif fmt not in _FMT_420 and fmt not in _FMT_422:
         a = np.ascontiguousarray(a, np.uint8)
     w, h, stride = _frame_geom(a, fmt)
     return np.ascontiguousarray(a, np.uint8), w, h, stride
@@ -672,9 +739,10 @@ class Encoder:
     def set_input_format(self, fmt: int, plane_stride: int = 0) -> None:
         """Input layout of the following encodes (JPGE_FMT_*): frames are then (H, W, 3),
         (H, W, 4) or, planar, (3, H, W); GRAY8: (H, W), written as a one-component JPEG;
-        NV12 and I420: pack_yuv420 frames.  plane_stride:
+        NV12 and I420: pack_yuv420 frames; YUYV, UYVY, NV16 and I422: pack_yuv422 frames.  plane_stride:
         bytes between the planes of the raw-pointer entries' planar frames (NV12, I420: from
-        the Y plane to the chroma; 0 = stride * height)."""
+        the Y plane to the chroma, as for NV16 and I422; 0 = stride * height; the packed 4:2:2
+        layouts are one plane and take 0)."""
         _check(lib().jpge_set_input_format(self._ctx, int(fmt), int(plane_stride)), "set_input_format")
         self._fmt = int(fmt)
 
@@ -703,7 +771,7 @@ class Encoder:
 
     def set_yuv_transform(self, preset: int, coeffs=None) -> None:
         """Sample transform of the following encodes of Y, Cb, Cr and gray frames (NV12, I420,
-        YUV444_PLANAR, GRAY8; encode*, encode_tensor_yuv, a 2-D encode_tensor, fdct_quant,
+        YUV444_PLANAR, YUYV, UYVY, NV16, I422, GRAY8; encode*, encode_tensor_yuv, encode_tensor_yuv422, a 2-D encode_tensor, fdct_quant,
         symbol_stats): JPGE_YUV_FULL_601 (the default: a sample v is v - 128), LIMITED_601,
         LIMITED_709, FULL_709, or JPGE_YUV_CUSTOM with coeffs = (y_off, m0, ..., m6).  The
         conversion runs inside the transform kernel; the RGB layouts ignore the setting."""
@@ -887,6 +955,104 @@ class Encoder:
             if cr.data_ptr() - c.data_ptr() != plane_stride:
                 raise ValueError("the Y, Cb and Cr planes must be equally spaced")
             least = w
+        if stride < least:
+            raise ValueError("rows overlap")
+        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
+        host_out = None
+        if out is None:
+            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            out_ptr, cap = _p(host_out), host_out.size
+        else:
+            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out: a contiguous uint8 device tensor")
+            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
+        prev = self.input_format()
+        self.set_input_format(fmt, plane_stride)
+        try:
+            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
+        finally:
+            self.set_input_format(*prev)
+        return n if host_out is None else host_out[:n].tobytes()
+
+    def encode_tensor_yuv422(self, y_or_packed, cbcr_or_cb=None, cr=None, quality: int = 50, out=None,
+                             layout=None):
+        """One 4:2:2 frame of torch uint8 tensors (a capture buffer or a 4:2:2 decoder's surface;
+        full-range BT.601 samples, or what set_yuv_transform says they are) through
+        jpge_encode_rgb8, read in place: a packed (H, W, 2) tensor with layout="yuyv" or "uyvy"
+        (W even: a pixel's two bytes are its Y and one chroma sample of its pair; an odd width
+        goes through encode_ptr); (H, W) + (H, cw, 2) is NV16; (H, W) + two (H, cw) is I422
+        (cw: W halved, rounded up).  The planes must be views of one allocation, all on one
+        device, at offsets the layout can express (jpge.h): unit inner strides, the chroma
+        after the Y plane, NV16's Cb,Cr rows at the Y pitch, I422's Cb and Cr rows at pitch
+        (Y pitch + 1) / 2 with Cr H rows after Cb; else ValueError.  Every subsampling mode
+        takes these layouts (422 is the native one).  Returns the .jpg bytes, or, with `out` a
+        uint8 tensor on the frame's device, writes them there and returns their length.  The
+        encoder's input layout is the same afterwards."""
+        y = y_or_packed
+        planes = [p for p in (y, cbcr_or_cb, cr) if p is not None]
+        for p in planes:
+            if p.element_size() != 1 or p.dtype.is_floating_point or p.device != y.device:
+                raise ValueError("encode_tensor_yuv422 takes uint8 tensors on one device")
+        plane_stride = 0
+        if y.dim() == 3:  # packed
+            if layout not in ("yuyv", "uyvy"):
+                raise ValueError(f"layout {layout!r}: a packed (H, W, 2) tensor is 'yuyv' or 'uyvy'")
+            if cbcr_or_cb is not None or cr is not None:
+                raise ValueError("a packed frame is one tensor")
+            if y.shape[2] != 2 or y.numel() == 0:
+                raise ValueError(f"packed frame of shape {tuple(y.shape)}: (H, W, 2)")
+            h, w = int(y.shape[0]), int(y.shape[1])
+            if w % 2:
+                raise ValueError(f"packed frame of odd width {w}: a (H, W, 2) tensor cannot hold the last group")
+            if y.stride(2) != 1 or y.stride(1) != 2:
+                raise ValueError(f"strides {tuple(y.stride())}: the inner dimensions must be packed")
+            stride = y.stride(0) if h > 1 else 2 * w
+            least = 2 * w
+            fmt = JPGE_FMT_YUYV if layout == "yuyv" else JPGE_FMT_UYVY
+        else:
+            if layout is not None:
+                raise ValueError("layout goes with a packed (H, W, 2) tensor")
+            if y.dim() != 2 or y.numel() == 0:
+                raise ValueError(f"Y plane of shape {tuple(y.shape)}: (H, W)")
+            h, w = int(y.shape[0]), int(y.shape[1])
+            cw = (w + 1) // 2
+            c = cbcr_or_cb
+            if c is not None and cr is None and tuple(c.shape) == (h, cw, 2):
+                fmt = JPGE_FMT_NV16
+            elif c is not None and cr is not None and tuple(c.shape) == (h, cw) == tuple(cr.shape):
+                fmt = JPGE_FMT_I422
+            else:
+                raise ValueError(f"chroma of shapes {[tuple(p.shape) for p in planes[1:]]} for a {w}x{h} Y plane: "
+                                 f"({h}, {cw}, 2) or two ({h}, {cw})")
+            store = y.untyped_storage().data_ptr()
+            if any(p.untyped_storage().data_ptr() != store for p in planes):
+                raise ValueError("the planes must be views of one allocation")
+            def pitch(p):  # a plane's row pitch (None: one row, any pitch)
+                if p.stride(1) != 1 and p.shape[1] > 1:
+                    raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
+                return p.stride(0) if p.shape[0] > 1 else None
+            stride = pitch(y)
+            plane_stride = c.data_ptr() - y.data_ptr()
+            if plane_stride <= 0:
+                raise ValueError("the chroma must follow the Y plane in memory")
+            if fmt == JPGE_FMT_NV16:
+                if c.stride(2) != 1 or (c.stride(1) != 2 and cw > 1):
+                    raise ValueError(f"strides {tuple(c.stride())}: Cb,Cr pairs must be packed")
+                cp = c.stride(0) if h > 1 else None
+                stride = stride if stride is not None else 2 * cw
+                if cp is not None and cp != stride:
+                    raise ValueError(f"chroma pitch {cp}: NV16's Cb,Cr rows have the Y pitch {stride}")
+                least = 2 * cw
+            else:
+                cp, rp = pitch(c), pitch(cr)
+                if stride is None:
+                    stride = w
+                cs = (stride + 1) // 2
+                if any(q is not None and q != cs for q in (cp, rp)):
+                    raise ValueError(f"chroma pitches {cp}, {rp}: I422's are (Y pitch + 1) / 2 = {cs}")
+                if cr.data_ptr() - c.data_ptr() != cs * h:
+                    raise ValueError(f"the Cr plane must start {cs * h} bytes ({h} rows) after the Cb plane")
+                least = w
         if stride < least:
             raise ValueError("rows overlap")
         flags = JPGE_DEVICE_INPUT if y.is_cuda else 0

@@ -172,7 +172,7 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
 #define JPGE_K1_SHAPE 0
 #endif
 constexpr int kShape = JPGE_K1_SHAPE;
-static_assert(kShape >= kShapeRgb8 && kShape <= kShapeGray, "JPGE_K1_SHAPE");
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapeI422, "JPGE_K1_SHAPE");
 // The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
 // layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
 // conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
@@ -184,7 +184,15 @@ static_assert(kShape >= kShapeRgb8 && kShape <= kShapeGray, "JPGE_K1_SHAPE");
 constexpr bool kYuv = kShape >= kShapeNv12;
 constexpr bool kGray = kShape == kShapeGray;
 constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420;
-constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
+// The 4:2:2 shapes (YUYV / UYVY, NV16, I422) stage the same words, a cell's chroma sample in
+// both of its pixels (cell x >> 1 of the pixel's own row), and have every instance the planar
+// 4:4:4 shape has: each mode's filter then runs on the chroma-repeated frame.  In 4:2:2 the
+// row-8 kernel keeps the first word of each pair: the cell's sample, no arithmetic.
+constexpr bool kPacked422 = kShape == kShapePacked422;
+constexpr bool kPlanes422 = kShape == kShapeNv16 || kShape == kShapeI422;  // chroma loads of their own, row = pixel row
+constexpr bool kPairs = kShape == kShapeNv12 || kShape == kShapeNv16;      // Cb,Cr byte pairs
+constexpr bool kHalfPitch = kShape == kShapeI420 || kShape == kShapeI422;  // chroma pitch (stride + 1) / 2
+constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kPacked422 ? 2u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
 constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
 constexpr uint32_t kSelRgbx = 0x0C020100u, kSelBgrx = 0x0C000102u;  // perm selectors of a 4-byte pixel (0x0c: zero)
 
@@ -214,13 +222,22 @@ __device__ __forceinline__ void unpack_run(const uint4& v0, const uint4& v1, con
         }
     }
 }
+// The packed 4:2:2 shape's run: v0, v1 its 8 groups of 4 bytes, Y0 Cb Y1 Cr or Cb Y0 Cr Y1.
+// sel4 selects Y0, Cb, Cr of a group (the even pixel); the odd pixel's Y1 lies two bytes on.
+constexpr uint32_t kSelYuyv = 0x0C030100u, kSelUyvy = 0x0C020001u;
+__device__ __forceinline__ void unpack_packed422(const uint4& v0, const uint4& v1, uint32_t sel4, uint32_t px[16]) {
+    const uint32_t wd[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) px[i] = __builtin_amdgcn_perm(0u, wd[i >> 1], sel4 + 2u * (uint32_t)(i & 1));
+}
 // The 4:2:0 layouts' run: v0 the 16 Y bytes; NV12: v1 the 8 Cb,Cr pairs of the run's cells;
 // I420: v1, v2 16 Cb and 16 Cr bytes, of which the run's cells are the low (half = 0) or
-// high 8.  Pixel i takes the chroma of cell i / 2.
+// high 8.  Pixel i takes the chroma of cell i / 2.  (NV16 and I422: the same bytes, of the
+// pixels' own chroma row.)
 __device__ __forceinline__ void unpack_yuv420(const uint4& v0, const uint4& v1, const uint4& v2, uint32_t half,
                                               uint32_t px[16]) {
     const uint32_t y[4] = {v0.x, v0.y, v0.z, v0.w};
-    if constexpr (kShape == kShapeNv12) {
+    if constexpr (kPairs) {
         const uint32_t c[4] = {v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -283,11 +300,24 @@ __device__ __forceinline__ XfK xf_load(const FdctArgs& a) {
 // frame); a 4:2:0 layout's chroma of the pixel's cell (inside the chroma plane: the
 // clamped pixel's cell is the clamped cell).
 __device__ __forceinline__ uint32_t edge_yuv(const uint8_t* base, uint64_t stride, uint64_t plane_stride, uint32_t gh,
-                                             uint32_t sy, uint32_t sx) {
+                                             uint32_t sel4, uint32_t sy, uint32_t sx) {
+    if constexpr (kPacked422) {
+        // the pixel's group, by byte loads (it may be unaligned); the odd pixel's Y two bytes on
+        const uint8_t* p = base + (uint64_t)sy * stride + 4 * (uint64_t)(sx >> 1);
+        const uint32_t w = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+        return __builtin_amdgcn_perm(0u, w, sel4 + 2u * (sx & 1));
+    }
     const uint32_t yv = base[(uint64_t)sy * stride + sx];
     const uint8_t* c = base + plane_stride;
     if constexpr (kGray) {
         return yv;
+    } else if constexpr (kShape == kShapeNv16) {
+        c += (uint64_t)sy * stride + 2 * (uint64_t)(sx >> 1);
+        return yv | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16);
+    } else if constexpr (kShape == kShapeI422) {
+        const uint64_t cs = (stride + 1) / 2;
+        c += (uint64_t)sy * cs + (sx >> 1);
+        return yv | ((uint32_t)c[0] << 8) | ((uint32_t)c[cs * gh] << 16);
     } else if constexpr (kShape == kShapeNv12) {
         c += (uint64_t)(sy >> 1) * stride + 2 * (uint64_t)(sx >> 1);
         return yv | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16);
@@ -320,13 +350,15 @@ __device__ __forceinline__ uint32_t edge_pixel(const uint8_t* rgb, uint64_t stri
 // inside their row, so the range is the last row's end.
 struct RgbRsrc {
     __amdgpu_buffer_rsrc_t p0;
-#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7
-    __amdgpu_buffer_rsrc_t p1, p2;  // (NV12: p2 repeats p1, unused)
+#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7 && JPGE_K1_SHAPE != 8
+    __amdgpu_buffer_rsrc_t p1, p2;  // (NV12, NV16: p2 repeats p1, unused)
 #endif
 };
 __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride, uint64_t plane_stride, uint32_t gw,
                                             uint32_t gh) {
-    const int range = (int)(uint32_t)((uint64_t)stride * (gh - 1) + (uint64_t)kBpp * gw);
+    // (packed 4:2:2: a row is ceil(gw / 2) whole groups)
+    const int range =
+        (int)(uint32_t)((uint64_t)stride * (gh - 1) + (kPacked422 ? 4 * (uint64_t)((gw + 1) / 2) : (uint64_t)kBpp * gw));
     uint8_t* b = const_cast<uint8_t*>(rgb);
     RgbRsrc r;
     r.p0 = __builtin_amdgcn_make_buffer_rsrc(b, 0, range, 0x00020000);
@@ -346,20 +378,36 @@ __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride,
     const int crange = (int)(uint32_t)(cs * (ch - 1) + cw);
     r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, crange, 0x00020000);
     r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride + cs * ch, 0, crange, 0x00020000);
+#elif JPGE_K1_SHAPE == 9
+    // the Cb,Cr plane: gh rows of pitch stride, 2 * cw bytes each
+    const uint32_t cw = (gw + 1) / 2;
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, (int)(uint32_t)(stride * (gh - 1) + 2 * (uint64_t)cw),
+                                             0x00020000);
+    r.p2 = r.p1;
+#elif JPGE_K1_SHAPE == 10
+    // the Cb plane, then the Cr plane: gh rows of pitch cs, cw bytes each
+    const uint32_t cw = (gw + 1) / 2;
+    const uint64_t cs = (stride + 1) / 2;
+    const int crange = (int)(uint32_t)(cs * (gh - 1) + cw);
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, crange, 0x00020000);
+    r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride + cs * gh, 0, crange, 0x00020000);
 #endif
     return r;
 }
-// the lane's run at buffer offset off (kOob: zeros); the 4:2:0 layouts' chroma at coff
+// the lane's run at buffer offset off (kOob: zeros); the 4:2:0, NV16 and I422 layouts' chroma at coff
 __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32_t coff, uint4& v0, uint4& v1, uint4& v2,
                                          uint4& v3) {
 #if JPGE_K1_SHAPE == 3 || JPGE_K1_SHAPE == 6
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, off, 0, 0));
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, off, 0, 0));
-#elif JPGE_K1_SHAPE == 4
+#elif JPGE_K1_SHAPE == 4 || JPGE_K1_SHAPE == 9
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff, 0, 0));
-#elif JPGE_K1_SHAPE == 5
+#elif JPGE_K1_SHAPE == 8
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
+#elif JPGE_K1_SHAPE == 5 || JPGE_K1_SHAPE == 10
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff, 0, 0));
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, coff, 0, 0));
@@ -387,12 +435,16 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || (kYuv && !kGray)) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
     if constexpr (kShape == kShapeX4) {
         sel4_ = a.fmt == kFmtBgra8 ? kSelBgrx : kSelRgbx;
+        asm volatile("" : "+s"(sel4_));
+    }
+    if constexpr (kPacked422) {
+        sel4_ = a.fmt == kFmtUyvy ? kSelUyvy : kSelYuyv;
         asm volatile("" : "+s"(sel4_));
     }
     XfK xf{};  // (the Y, Cb, Cr shapes' !kExact instances)
@@ -406,8 +458,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     const uint32_t tiles_per_row = (mw + 3) / 4;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    // (I420: the chroma pitch, half the stride, is 16-byte aligned too)
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (kShape != kShapeI420 || (stride_ & 31) == 0);
+    // (I420, I422: the chroma pitch, half the stride, is 16-byte aligned too)
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!kHalfPitch || (stride_ & 31) == 0);
     const int r16 = lane >> 2, c16 = lane & 3;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;     // DCT: lane -> (block of the round, column)
 
@@ -444,6 +496,11 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         cpitch = kShape == kShapeNv12 ? (uint32_t)stride_ : (uint32_t)((stride_ + 1) / 2);
         lane_coff = (uint32_t)(r16 >> 1) * cpitch + (kShape == kShapeNv12 ? (uint32_t)c16 : (uint32_t)(c16 >> 1)) * 16;
     }
+    // NV16, I422: the same bytes of chroma row (tile row * 16 + r16), the pixels' own
+    if constexpr (kPlanes422) {
+        cpitch = kPairs ? (uint32_t)stride_ : (uint32_t)((stride_ + 1) / 2);
+        lane_coff = (uint32_t)r16 * cpitch + (kPairs ? (uint32_t)c16 : (uint32_t)(c16 >> 1)) * 16;
+    }
     auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * 4;
@@ -451,11 +508,16 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
         // (I420: and the 16 chroma bytes lie inside their row)
         if constexpr (kShape == kShapeI420) ok = ok && ((xs >> 5) + 1) * 16 <= (gw_ + 1) / 2;
+        if constexpr (kShape == kShapeI422) ok = ok && ((xs >> 5) + 1) * 16 <= (gw_ + 1) / 2;
         const uint32_t base = (uint32_t)((uint64_t)(mrow * 16) * stride_ + (uint64_t)mcol0 * kRun);  // (uniform)
         const uint32_t off = ok ? base + lane_off : kOob;
         uint32_t coff = kOob;
         if constexpr (kYuv420) {
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kShape == kShapeNv12 ? 16 : 8));
+            coff = ok ? cbase + lane_coff : kOob;
+        }
+        if constexpr (kPlanes422) {
+            const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 16) * cpitch + (uint64_t)mcol0 * (kPairs ? 16 : 8));
             coff = ok ? cbase + lane_coff : kOob;
         }
         load_run(rgb_rs, off, coff, v0, v1, v2, v3);
@@ -621,8 +683,10 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         // (the prefetched registers are consumed on every path, so no later wait on
         // them can also drain the previous tile's coefficient stores)
         uint32_t px[16];
-        if constexpr (kYuv420) {
+        if constexpr (kYuv420 || kPlanes422) {
             unpack_yuv420(c0, c1, c2, (uint32_t)(c16 & 1), px);
+        } else if constexpr (kPacked422) {
+            unpack_packed422(c0, c1, sel4_, px);
         } else if constexpr (kShape == kShapeX4 || kShape == kShapePlanar || kShape == kShapeYuv444) {
             unpack_run(c0, c1, c2, c3, sel4_, px);
         } else {
@@ -639,7 +703,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         if (!cfast) {  // right/bottom edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
             if constexpr (kYuv)
-                for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sy, min(xs + i, gw_ - 1));
+                for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sel4_, sy, min(xs + i, gw_ - 1));
             else
                 for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
@@ -743,12 +807,16 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || (kYuv && !kGray)) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
     if constexpr (kShape == kShapeX4) {
         sel4_ = a.fmt == kFmtBgra8 ? kSelBgrx : kSelRgbx;
+        asm volatile("" : "+s"(sel4_));
+    }
+    if constexpr (kPacked422) {
+        sel4_ = a.fmt == kFmtUyvy ? kSelUyvy : kSelYuyv;
         asm volatile("" : "+s"(sel4_));
     }
     XfK xf{};  // (the Y, Cb, Cr shapes' !kExact instances)
@@ -766,8 +834,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     const uint32_t tiles_per_row = (mw + kMcus - 1) / kMcus;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    // (I420: the chroma pitch, half the stride, is 16-byte aligned too)
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (kShape != kShapeI420 || (stride_ & 31) == 0);
+    // (I420, I422: the chroma pitch, half the stride, is 16-byte aligned too)
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!kHalfPitch || (stride_ & 31) == 0);
     const int r8 = lane >> 3, c8 = lane & 7;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;   // DCT: lane -> (block of the round, column)
 
@@ -784,14 +852,29 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         return __builtin_amdgcn_readfirstlane(v);
     };
     const uint32_t lane_off = (uint32_t)r8 * (uint32_t)stride_ + (uint32_t)c8 * kRun;  // (as in fdct_kernel)
+    // NV16, I422: the chroma of the run's 8 cells, in the pixels' own chroma row of pitch cpitch:
+    // NV16 the 16 bytes under the run, I422 the 16 bytes that hold its 8
+    uint32_t cpitch = 0, lane_coff = 0;
+    if constexpr (kPlanes422) {
+        cpitch = kPairs ? (uint32_t)stride_ : (uint32_t)((stride_ + 1) / 2);
+        lane_coff = (uint32_t)r8 * cpitch + (kPairs ? (uint32_t)c8 : (uint32_t)(c8 >> 1)) * 16;
+    }
     auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * kMcus;
         const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
-        const bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
+        bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
+        // (I422: and the 16 chroma bytes lie inside their row)
+        if constexpr (kShape == kShapeI422) ok = ok && ((xs >> 5) + 1) * 16 <= (gw_ + 1) / 2;
         const uint32_t base = (uint32_t)((uint64_t)(mrow * 8) * stride_ + (uint64_t)mcol0 * (kRun / 2) * kYh);  // (uniform)
         const uint32_t off = ok ? base + lane_off : kOob;
-        load_run(rgb_rs, off, kOob, v0, v1, v2, v3);
+        uint32_t coff = kOob;
+        if constexpr (kPlanes422) {
+            // the tile's 128 px: 128 bytes of Cb,Cr pairs (NV16), or 64 of each plane (I422)
+            const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kPairs ? 8 : 4) * kYh);
+            coff = ok ? cbase + lane_coff : kOob;
+        }
+        load_run(rgb_rs, off, coff, v0, v1, v2, v3);
         return ok;
     };
     u32x4 pend;
@@ -841,6 +924,10 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         uint32_t px[16];
         if constexpr (kGray) {
             unpack_gray(c0, px);
+        } else if constexpr (kPlanes422) {
+            unpack_yuv420(c0, c1, c2, (uint32_t)(c8 & 1), px);
+        } else if constexpr (kPacked422) {
+            unpack_packed422(c0, c1, sel4_, px);
         } else if constexpr (kShape == kShapeX4 || kShape == kShapePlanar || kShape == kShapeYuv444) {
             unpack_run(c0, c1, c2, c3, sel4_, px);
         } else {
@@ -857,7 +944,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         if (!cfast) {  // edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
             if constexpr (kYuv)
-                for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sy, min(xs + i, gw_ - 1));
+                for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sel4_, sy, min(xs + i, gw_ - 1));
             else
                 for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
@@ -1019,7 +1106,8 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
 }
 
 #if JPGE_K1_SHAPE != 0
-// this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray)
+// this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
+// _packed422 / _nv16 / _i422)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
@@ -1031,6 +1119,9 @@ hipError_t launch_fdct_nv12(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid
 hipError_t launch_fdct_i420(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_yuv444(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_gray(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_packed422(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_nv16(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_i422(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 
 uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs) {
     const uint32_t tiles = k1_tiles(g);
@@ -1054,7 +1145,7 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         // 32-bit buffer offsets: the frame's pixels and coefficients must stay below kOob
         // (a 16384^2 frame needs 805 MB of each)
         // (planar: each plane has its own descriptor, so the extent is one plane's)
-        // (the 4:2:0 layouts' chroma planes have descriptors of their own, with smaller extents)
+        // (the 4:2:0, NV16 and I422 layouts' chroma planes have descriptors of their own, with no larger extents)
         // (a one-component geometry goes with the gray layout, and only with it)
         if (!fmt_valid(m.fmt) || m.g.height == 0 || ((fmt_yuv(m.fmt) || fmt_gray(m.fmt)) && m.maxval != 255) ||
             fmt_gray(m.fmt) != m.g.gray())
@@ -1083,6 +1174,9 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         case kShapeI420: return launch_fdct_i420(w, grid, s, t);
         case kShapeYuv444: return launch_fdct_yuv444(w, grid, s, t);
         case kShapeGray: return launch_fdct_gray(w, grid, s, t);
+        case kShapePacked422: return launch_fdct_packed422(w, grid, s, t);
+        case kShapeNv16: return launch_fdct_nv16(w, grid, s, t);
+        case kShapeI422: return launch_fdct_i422(w, grid, s, t);
         default: return launch_fdct_planar(w, grid, s, t);
     }
 }

@@ -59,15 +59,23 @@ constexpr int kFmtRgb8 = 0, kFmtBgr8 = 1, kFmtRgba8 = 2, kFmtBgra8 = 3, kFmtRgb8
 // NV12 (Y plane + one plane of interleaved Cb,Cr at half size), I420 (Y, Cb, Cr planes,
 // chroma at half size), planar 4:4:4 (addressed as kFmtRgb8Planar)
 constexpr int kFmtNv12 = 16, kFmtI420 = 17, kFmtYuv444Planar = 18;
+// 4:2:2 frames of the same samples, one Cb and one Cr per horizontal pixel pair (cell x >> 1) of
+// every row: packed groups Y0 Cb Y1 Cr (YUYV) or Cb Y0 Cr Y1 (UYVY), NV16 (Y plane + a plane of
+// interleaved Cb,Cr rows), I422 (Y, Cb, Cr planes).  A frame is the planar 4:4:4 frame whose
+// chroma planes hold c[y][x >> 1] at pixel (y, x), in every subsampling mode.
+constexpr int kFmtYuyv = 20, kFmtUyvy = 21, kFmtNv16 = 22, kFmtI422 = 23;
 // one plane of 8-bit luminance samples (a sample v is the fp64 value v - 128, as a Y sample
 // above): a one-component stream, Geometry::gray(), whatever the subsampling mode
 constexpr int kFmtGray8 = 8;
 JPGE_HD inline bool fmt_valid(int fmt) {
-    return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar);
+    return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar) ||
+           (fmt >= kFmtYuyv && fmt <= kFmtI422);
 }
 JPGE_HD inline bool fmt_gray(int fmt) { return fmt == kFmtGray8; }
 JPGE_HD inline bool fmt_yuv(int fmt) { return fmt >= kFmtNv12; }
 JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420; }  // chroma planes at half size
+JPGE_HD inline bool fmt_yuv422(int fmt) { return fmt >= kFmtYuyv && fmt <= kFmtI422; }  // chroma at half width, every row
+JPGE_HD inline bool fmt_packed422(int fmt) { return fmt == kFmtYuyv || fmt == kFmtUyvy; }
 constexpr int kShapeRgb8 = 0;    // 48 bytes R,G,B,...: three b128 loads
 constexpr int kShapeBgr8 = 1;    // the same loads, bytes 2,1,0 of each pixel
 constexpr int kShapeX4 = 2;      // RGBA8 / BGRA8: 64 bytes, four b128 loads, a wave-uniform byte selector
@@ -76,22 +84,28 @@ constexpr int kShapeNv12 = 4;    // 16 Y bytes + the 16 Cb,Cr bytes (8 samples o
 constexpr int kShapeI420 = 5;    // 16 Y bytes + 16 Cb bytes + 16 Cr bytes (the lane uses 8 of each): three b128 loads
 constexpr int kShapeYuv444 = 6;  // the planar shape's loads of the planes Y, Cb, Cr
 constexpr int kShapeGray = 7;    // 16 Y bytes: one b128 load (no chroma: Geometry::gray())
+constexpr int kShapePacked422 = 8;  // YUYV / UYVY: the run's 32 bytes, two b128 loads, wave-uniform byte selectors
+constexpr int kShapeNv16 = 9;    // the NV12 shape's two loads, the Cb,Cr row that of the pixels
+constexpr int kShapeI422 = 10;   // the I420 shape's three loads, the chroma rows those of the pixels
 JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
+    return fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
          : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
 }
 // bytes per pixel within a row (planar: of one plane), and planes
-JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
-JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt == kFmtNv12 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
+JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt_packed422(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
+JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
 // The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
-// that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs).
+// that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs; NV16 likewise; the packed
+// 4:2:2 layouts: ceil(width / 2) whole 4-byte groups).
 JPGE_HD inline uint64_t fmt_row_bytes(int fmt, uint32_t width) {
-    return fmt == kFmtNv12 ? ((uint64_t)width + 1) & ~(uint64_t)1 : (uint64_t)fmt_bpp(fmt) * width;
+    if (fmt_packed422(fmt)) return 4 * (((uint64_t)width + 1) / 2);
+    return fmt == kFmtNv12 || fmt == kFmtNv16 ? ((uint64_t)width + 1) & ~(uint64_t)1 : (uint64_t)fmt_bpp(fmt) * width;
 }
 // The 4:2:0 layouts' chroma: ceil(height / 2) rows of ceil(width / 2) samples, starting
 // plane_stride bytes after the Y plane; row pitch `stride` (NV12, 2 bytes per sample) or
-// (stride + 1) / 2 (I420, whose Cr plane follows the Cb plane's rows).
-JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) { return fmt == kFmtI420 ? (stride + 1) / 2 : stride; }
+// (stride + 1) / 2 (I420, whose Cr plane follows the Cb plane's rows).  NV16 and I422: the
+// same pitches and order, `height` rows of ceil(width / 2) samples.
+JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) { return fmt == kFmtI420 || fmt == kFmtI422 ? (stride + 1) / 2 : stride; }
 JPGE_HD inline uint32_t chroma_dim(uint32_t n) { return (n + 1) / 2; }
 
 constexpr int kHistReplicas = 8;  // spread of the global histogram atomics
@@ -128,7 +142,7 @@ struct FdctArgs {
     uint32_t imp_n16;
     uint64_t* dbg;   // diagnostic phase stamps (JPGE_STAMPS builds), else unused
     // input layout (kFmt*); planar: plane c's rows start at rgb + c * plane_stride
-    // (NV12, I420: the chroma starts at rgb + plane_stride, see fmt_chroma_pitch)
+    // (NV12, I420, NV16, I422: the chroma starts at rgb + plane_stride, see fmt_chroma_pitch)
     int fmt = kFmtRgb8;
     // 1: the Y, Cb, Cr and gray shapes convert each sample by xf (jpge_set_yuv_transform, a
     // preset other than FULL_601): their !kExact instances.  The other shapes ignore it.

@@ -46,7 +46,8 @@ typedef struct jpge_ctx jpge_ctx;
 typedef struct {
     const uint8_t* rgb; /* interleaved RGB8 (host, or device with JPGE_DEVICE_INPUT) */
     uint32_t width, height;
-    size_t stride;      /* bytes per row, 0 = width*3 */
+    size_t stride;      /* bytes per row, 0 = width*3; stride * height (of one plane) must stay below
+                           0xFFFFFF00, the transform kernel's 32-bit offset range, else JPGE_E_ARG */
     int maxval;         /* PPM maxval, 1..255; samples are scaled by 255./maxval (Image.cpp:465) */
     uint8_t* out;       /* .jpg destination */
     size_t cap;         /* capacity of out */

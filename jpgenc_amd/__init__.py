@@ -611,7 +611,15 @@ def pack_yuv422(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
 def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     """(width, height, row stride in bytes) of a C-contiguous frame shaped for layout `fmt`:
     (H, W, 3), (H, W, 4) or (3, H, W); GRAY8: (H, W); NV12 and I420: a pack_yuv420 frame of
-    that layout; YUYV, UYVY, NV16 and I422: a pack_yuv422 frame of that layout."""
+    that layout; YUYV, UYVY, NV16 and I422: a pack_yuv422 frame of that layout.  A width or
+    height of 0 or above 65535 (a JPEG frame header's limit) is a ValueError."""
+    w, h, stride = _frame_geom_any(a, fmt)
+    if not (1 <= w <= 65535 and 1 <= h <= 65535):
+        raise ValueError(f"a {w}x{h} frame: width and height are 1..65535")
+    return w, h, stride
+
+
+def _frame_geom_any(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     bpp, planes = input_format_info(fmt)
     if fmt == JPGE_FMT_GRAY8:
         if a.ndim != 2 or a.dtype != np.uint8 or a.size == 0:
@@ -1094,6 +1102,11 @@ class Encoder:
         st = lib().jpge_encode_batch(self._ctx, arr, len(frames), q[2], q[3], int(flags))
         _check(st, "encode_batch")
         return [f.len for f in arr]
+
+    def batch_status(self) -> list[int]:
+        """The status of each frame of the last encode_batch_dev call (jpge_frame.status): when the
+        call raised, the frames that were refused or failed; 0 for the others."""
+        return [] if self._desc is None else [int(f.status) for f in self._desc[1]]
 
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         qy, qc = self._tables(quality, None, None)

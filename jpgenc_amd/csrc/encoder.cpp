@@ -717,6 +717,9 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     const size_t cpitch = (size_t)fmt_chroma_pitch(f.fmt, stride), dev_cpitch = (size_t)fmt_chroma_pitch(f.fmt, dev_pitch);
     const size_t dev_bytes = half ? dev_plane + (planes - 1) * dev_cpitch * crows : planes * dev_plane;
     const bool dev_in = (flags & kFlagDeviceInput) != 0, dev_out = (flags & kFlagDeviceOutput) != 0;
+    // the kernel's 32-bit offsets must span the frame it reads (a device frame in place at its
+    // own pitch, a host frame's copy): refused here, before a slot grows or anything is queued
+    if (!k1_offsets_fit(f.fmt, g, dev_in ? stride : dev_pitch)) return kErrArg;
     const size_t in_bytes = dev_in ? 0 : dev_bytes;
     const size_t out_cap = dev_out ? 0 : max_jpeg_bytes(f.width, f.height);
     if (!tables_nonzero(qy, qc)) return kErrArg;

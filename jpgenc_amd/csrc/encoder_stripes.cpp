@@ -25,6 +25,7 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     if (!tables_nonzero(qy, qc)) return kErrArg;
     const uint32_t hs = std::min(16 * d.mcu_rows, d.height - 16 * d.mcu_row0);
     const Geometry g = geometry(d.width, hs);
+    if (!k1_offsets_fit(fmt_, g, stride)) return kErrArg;  // (the kernel's 32-bit offsets span the stripe)
     // restart intervals: the stripe must start one (its bytes are then its own)
     if (restart_mcus_ && ((uint64_t)d.mcu_row0 * g.mw) % restart_mcus_ != 0) return kErrArg;
     Slot& s = slot0();

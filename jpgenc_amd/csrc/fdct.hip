@@ -1150,11 +1150,8 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         if (!fmt_valid(m.fmt) || m.g.height == 0 || ((fmt_yuv(m.fmt) || fmt_gray(m.fmt)) && m.maxval != 255) ||
             fmt_gray(m.fmt) != m.g.gray())
             return hipErrorInvalidValue;
-        const uint64_t row = fmt_row_bytes(m.fmt, m.g.width);
-        const uint64_t extent = m.stride * (m.g.height - 1) + row;  // the descriptor's range
-        if (m.stride < row || extent >= kOob || (uint64_t)m.stride * m.g.height >= kOob ||
-            (uint64_t)m.g.nblocks() * 128 >= kOob)
-            return hipErrorInvalidValue;
+        static_assert(kK1OffsetBound == kOob, "the host's bound is the kernel's out-of-range offset");
+        if (!k1_offsets_fit(m.fmt, m.g, m.stride)) return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
             fmt_shape(m.fmt) != fmt_shape(a.fmt) || (m.xf_on != 0) != (a.xf_on != 0) ||
             m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs))

@@ -107,6 +107,18 @@ JPGE_HD inline uint64_t fmt_row_bytes(int fmt, uint32_t width) {
 // same pitches and order, `height` rows of ceil(width / 2) samples.
 JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) { return fmt == kFmtI420 || fmt == kFmtI422 ? (stride + 1) / 2 : stride; }
 JPGE_HD inline uint32_t chroma_dim(uint32_t n) { return (n + 1) / 2; }
+// The transform kernel reaches a frame's pixels and its coefficients through 32-bit buffer
+// offsets: stride * height (planar layouts: of one plane; each plane has a descriptor of its
+// own, the chroma planes' extents are no larger) and nblocks * 128 must stay below this bound
+// (fdct.hip's out-of-range offset).  The frame entries refuse a frame that does not fit
+// with the argument error, before anything is queued (jpge.h, jpge_frame.stride).
+constexpr uint64_t kK1OffsetBound = 0xFFFFFF00u;
+inline bool k1_offsets_fit(int fmt, const Geometry& g, uint64_t stride) {
+    const uint64_t row = fmt_row_bytes(fmt, g.width);
+    if (g.height == 0 || stride < row || stride >= kK1OffsetBound) return false;
+    const uint64_t extent = stride * (g.height - 1) + row;  // the descriptor's range
+    return extent < kK1OffsetBound && stride * g.height < kK1OffsetBound && (uint64_t)g.nblocks() * 128 < kK1OffsetBound;
+}
 
 constexpr int kHistReplicas = 8;  // spread of the global histogram atomics
 constexpr int kStatsTile = 128;           // blocks per statistics tile (4 lanes each)

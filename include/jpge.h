@@ -179,6 +179,35 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
 #define JPGE_FMT_UYVY 21
 #define JPGE_FMT_NV16 22
 #define JPGE_FMT_I422 23
+/* 10-bit 4:2:0 frames (HEVC Main10, AV1, VP9 profile 2 decoders): little-endian 16-bit words,
+ * NV12's and I420's planes.  `rgb` points at the Y plane and `stride` is its pitch in BYTES.
+ * With cw = ceil(width / 2), ch = ceil(height / 2):
+ *   P010: a sample is s = word >> 6; the low six bits are never read (P012 and P016 data is
+ *     taken at its top 10 bits).  The Cb,Cr plane at rgb + plane_stride (0 = stride * height):
+ *     ch rows of pitch `stride`, Cb in the even words and Cr in the odd words; stride 0 =
+ *     2 * (width rounded up to even).
+ *   I010 (yuv420p10le): a sample is s = word & 0x3FF; the high six bits are never read.  The
+ *     Cb plane at rgb + plane_stride (0 = stride * height): ch rows of pitch
+ *     cs = 2 * ceil(stride / 4); the Cr plane at Cb + cs * ch; stride 0 = 2 * width.
+ * The base, `stride` and `plane_stride` must be even and the stride not below the least for
+ * the width (else JPGE_E_ARG).  maxval must be 255 and the context in JPGE_S420_M, as for
+ * NV12; jpge_stripe_transform and jpge_group_encode_striped refuse the layouts.  The fast
+ * path needs base, stride and plane_stride 16-byte aligned (I010: a stride that is a multiple
+ * of 32); anything else that is even works, slower.
+ * Conversion: no sample is rounded to 8 bits.  A pixel's s_y, s_cb, s_cr (the chroma of its
+ * 2x2 cell, edge-replicated in the chroma domain as for NV12) enter as the exact values
+ *   yc = 0.25 * s_y - y_off,  u = 0.25 * s_cb - 128,  v = 0.25 * s_cr - 128
+ * and the three lines of jpge_set_yuv_transform (each product and sum rounded on its own,
+ * the clamps included) are applied ALWAYS: under JPGE_YUV_FULL_601 with the identity
+ * coefficients, which gives Y' = min(0.25 * s_y, 255) - 128 and Cb' = min(0.25 * s_cb - 128, 127).
+ * Studio swing in 10 bits (64..940, 64..960) is 4 times the 8-bit one, so the presets mean
+ * what they mean in 8 bits.  Full-range 10-bit data by ITU-T H.273 has white at 1023, which the
+ * identity clamps to 255; a caller who wants 1023 at 255 exactly passes JPGE_YUV_CUSTOM with
+ * m[0] = 1020.0 / 1023.
+ * A frame whose samples are all multiples of 4 gives, byte for byte, the .jpg of the NV12 / I420
+ * frame of s / 4: under every transform setting, Huffman mode and restart interval. */
+#define JPGE_FMT_P010 32
+#define JPGE_FMT_I010 33
 /* One plane of 8-bit luminance: `height` rows of `stride` bytes (0 = width), one byte per
  * pixel; a sample v enters the transform as the value v - 128, as a Y sample above.
  * maxval must be 255 and plane_stride 0 (else JPGE_E_ARG).  The output is a baseline JPEG
@@ -204,7 +233,7 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
  * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
  * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
- * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts and for
+ * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts, the two 10-bit layouts and for
  * JPGE_FMT_GRAY8 (stripes are three-component 4:2:0 of interleaved colour); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
 int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
 /* the current setting (plane_stride may be NULL) */

@@ -30,6 +30,11 @@ JPGE_FMT_RGB8, JPGE_FMT_BGR8, JPGE_FMT_RGBA8, JPGE_FMT_BGRA8, JPGE_FMT_RGB8_PLAN
 #: host frames from pack_yuv420), and planar (3, H, W)
 JPGE_FMT_NV12, JPGE_FMT_I420, JPGE_FMT_YUV444_PLANAR = 16, 17, 18
 _FMT_420 = (JPGE_FMT_NV12, JPGE_FMT_I420)
+#: 10-bit 4:2:0 frames of little-endian 16-bit words (jpge.h): P010 (NV12's planes, a sample in its
+#: word's top 10 bits) and I010 / yuv420p10le (I420's planes, a sample in the low 10 bits); a
+#: sample s enters the sample transform as s / 4, unrounded
+JPGE_FMT_P010, JPGE_FMT_I010 = 32, 33
+_FMT_420P10 = (JPGE_FMT_P010, JPGE_FMT_I010)
 #: 4:2:2 frames of the same samples (one Cb, Cr per horizontal pixel pair of every row): packed
 #: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 groups, NV16 (Y plane + Cb,Cr rows), I422 (three planes); host
 #: frames from pack_yuv422
@@ -551,6 +556,51 @@ def pack_yuv420(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     return f, w, h, stride
 
 
+def yuv420p10_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of a P010 or I010 frame with plane stride 0 (stride, in bytes, 0: the least one)."""
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    if fmt == JPGE_FMT_P010:
+        return (stride or 4 * cw) * (h + ch)
+    if fmt == JPGE_FMT_I010:
+        stride = stride or 2 * w
+        return stride * h + 2 * (2 * ((stride + 3) // 4)) * ch
+    raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:0 one")
+
+
+def pack_yuv420p10(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
+    """(frame, w, h, stride): the (H, W) Y plane and the (ceil(H/2), ceil(W/2)) Cb and Cr planes of
+    10-bit samples (uint16 values 0..1023) as one contiguous host frame of bytes in layout
+    JPGE_FMT_P010 (each sample in its word's top 10 bits, the low six zero) or JPGE_FMT_I010 with
+    the least stride and plane stride 0 (jpge.h).  The frame (a Yuv420Frame) is what encode,
+    encode_batch, fdct_quant and symbol_stats take when the input layout is `fmt`."""
+    y, cb, cr = (np.ascontiguousarray(p) for p in (y, cb, cr))
+    for p in (y, cb, cr):
+        if p.dtype.kind not in "ui" or (p.size and (int(p.min()) < 0 or int(p.max()) > 1023)):
+            raise ValueError("pack_yuv420p10 takes integer planes of 10-bit samples (0..1023)")
+    y, cb, cr = (p.astype("<u2") for p in (y, cb, cr))
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
+    h, w = y.shape
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    if cb.shape != (ch, cw) or cr.shape != (ch, cw):
+        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({ch}, {cw}) for a {w}x{h} frame")
+    if fmt == JPGE_FMT_P010:
+        stride = 4 * cw
+        buf = np.zeros((h + ch, 2 * cw), "<u2")  # (odd width: one pad word per Y row)
+        buf[:h, :w] = y << 6
+        buf[h:, 0::2] = cb << 6
+        buf[h:, 1::2] = cr << 6
+        buf = buf.reshape(-1)
+    elif fmt == JPGE_FMT_I010:
+        stride = 2 * w  # chroma pitch 2 * ceil(2 w / 4) = 2 * cw
+        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
+    else:
+        raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:0 one")
+    f = buf.view(np.uint8).view(Yuv420Frame)
+    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
+    return f, w, h, stride
+
+
 class Yuv422Frame(Yuv420Frame):
     """A host YUYV, UYVY, NV16 or I422 frame (pack_yuv422): the layout's bytes, planes back to
     back (plane stride 0), with the geometry that a flat buffer does not show."""
@@ -631,6 +681,11 @@ def _frame_geom_any(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
                 a.size != yuv420_bytes(fmt, a.width, a.height, a.stride):
             raise ValueError(f"input layout {fmt} takes a pack_yuv420({fmt}, y, cb, cr) frame")
         return a.width, a.height, a.stride
+    if fmt in _FMT_420P10:
+        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
+                a.size != yuv420p10_bytes(fmt, a.width, a.height, a.stride):
+            raise ValueError(f"input layout {fmt} takes a pack_yuv420p10({fmt}, y, cb, cr) frame")
+        return a.width, a.height, a.stride
     if fmt in _FMT_422:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
                 a.size != yuv422_bytes(fmt, a.width, a.height, a.stride):
@@ -647,7 +702,7 @@ def _as_frame(a, fmt: int):
     """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
     if fmt == JPGE_FMT_GRAY8:
         a = np.ascontiguousarray(a)  # (the type is checked, not converted: a float plane is no gray frame)
-    elif fmt not in _FMT_420 and fmt not in _FMT_422:
+    elif fmt not in _FMT_420 and fmt not in _FMT_422 and fmt not in _FMT_420P10:
         a = np.ascontiguousarray(a, np.uint8)
     w, h, stride = _frame_geom(a, fmt)
     return np.ascontiguousarray(a, np.uint8), w, h, stride
@@ -963,6 +1018,79 @@ class Encoder:
             if cr.data_ptr() - c.data_ptr() != plane_stride:
                 raise ValueError("the Y, Cb and Cr planes must be equally spaced")
             least = w
+        if stride < least:
+            raise ValueError("rows overlap")
+        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
+        host_out = None
+        if out is None:
+            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            out_ptr, cap = _p(host_out), host_out.size
+        else:
+            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out: a contiguous uint8 device tensor")
+            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
+        prev = self.input_format()
+        self.set_input_format(fmt, plane_stride)
+        try:
+            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
+        finally:
+            self.set_input_format(*prev)
+        return n if host_out is None else host_out[:n].tobytes()
+
+    def encode_tensor_yuv10(self, y, cbcr_or_cb, cr=None, quality: int = 50, out=None):
+        """One 10-bit 4:2:0 frame of 2-D 16-bit torch tensors (a Main10 decoder's surface), read in
+        place through jpge_encode_rgb8: (H, W) + (ch, 2 * cw) of interleaved Cb,Cr words is P010
+        (samples in the words' top 10 bits), (H, W) + two (ch, cw) is I010 (samples in the low
+        10 bits; ch, cw: H, W halved, rounded up).  The planes must be views of one allocation,
+        on one device, at offsets the layout can express (jpge.h): unit inner strides, the chroma
+        after the Y plane, P010's Cb,Cr rows at the Y pitch, I010's Cb and Cr rows at pitch
+        2 * ceil(Y pitch in bytes / 4) with Cr ch rows after Cb; else ValueError.  Needs
+        subsampling mode 420.  Returns the .jpg bytes, or, with `out` a uint8 tensor on the
+        frame's device, writes them there and returns their length.  The encoder's input layout
+        is the same afterwards."""
+        planes = [y, cbcr_or_cb] + ([] if cr is None else [cr])
+        for p in planes:
+            if p.element_size() != 2 or p.dtype.is_floating_point or p.dim() != 2 or p.device != y.device:
+                raise ValueError("encode_tensor_yuv10 takes 2-D 16-bit integer tensors on one device")
+        if y.numel() == 0:
+            raise ValueError(f"Y plane of shape {tuple(y.shape)}: (H, W)")
+        h, w = y.shape
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        c = cbcr_or_cb
+        if cr is None and tuple(c.shape) == (ch, 2 * cw):
+            fmt = JPGE_FMT_P010
+        elif cr is not None and tuple(c.shape) == (ch, cw) == tuple(cr.shape):
+            fmt = JPGE_FMT_I010
+        else:
+            raise ValueError(f"chroma of shape {tuple(c.shape)}" + ("" if cr is None else f", {tuple(cr.shape)}") +
+                             f" for a {w}x{h} Y plane: ({ch}, {2 * cw}) or two ({ch}, {cw})")
+        store = y.untyped_storage().data_ptr()
+        if any(p.untyped_storage().data_ptr() != store for p in planes):
+            raise ValueError("the planes must be views of one allocation")
+        def pitch(p):  # a plane's row pitch in bytes (None: one row, any pitch)
+            if p.stride(1) != 1 and p.shape[1] > 1:
+                raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
+            return 2 * p.stride(0) if p.shape[0] > 1 else None
+        stride = pitch(y)
+        plane_stride = c.data_ptr() - y.data_ptr()
+        if plane_stride <= 0:
+            raise ValueError("the chroma must follow the Y plane in memory")
+        if fmt == JPGE_FMT_P010:
+            cp = pitch(c)
+            stride = stride if stride is not None else cp if cp is not None else 4 * cw
+            if cp is not None and cp != stride:
+                raise ValueError(f"chroma pitch {cp}: P010's Cb,Cr rows have the Y pitch {stride}")
+            least = 4 * cw
+        else:
+            cp, rp = pitch(c), pitch(cr)
+            if stride is None:  # (one Y row: any pitch whose half is the chroma's)
+                stride = 2 * cp if cp is not None else 2 * rp if rp is not None else 2 * w
+            cs = 2 * ((stride + 3) // 4)
+            if any(q is not None and q != cs for q in (cp, rp)):
+                raise ValueError(f"chroma pitches {cp}, {rp}: I010's are 2 * ceil(Y pitch / 4) = {cs}")
+            if cr.data_ptr() - c.data_ptr() != cs * ch:
+                raise ValueError(f"the Cr plane must start {cs * ch} bytes ({ch} rows) after the Cb plane")
+            least = 2 * w
         if stride < least:
             raise ValueError("rows overlap")
         flags = JPGE_DEVICE_INPUT if y.is_cuda else 0

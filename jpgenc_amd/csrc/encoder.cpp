@@ -600,7 +600,8 @@ FdctArgs Encoder::fdct_args(Slot& s, int maxval, Slot* imp) {
     a.fmt = s.in_fmt;
     a.plane_stride = s.in_plane_stride;
     // the sample transform of Y, Cb, Cr and gray frames (FULL_601: the kExact instances)
-    a.xf_on = (fmt_yuv(s.in_fmt) || fmt_gray(s.in_fmt)) && yuv_preset_ != kYuvFull601 ? 1u : 0u;
+    // (10-bit samples always: FULL_601 runs it with the identity, for its clamps)
+    a.xf_on = ((fmt_yuv(s.in_fmt) || fmt_gray(s.in_fmt)) && yuv_preset_ != kYuvFull601) || fmt_yuv10(s.in_fmt) ? 1u : 0u;
     if (a.xf_on) {
         a.xf[0] = yuv_xf_.y_off;
         for (int i = 0; i < 7; ++i) a.xf[1 + i] = yuv_xf_.m[i];
@@ -699,6 +700,8 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     // Y, Cb, Cr samples are 8-bit, and half-size chroma planes are the S420_m mode's planes
     if (fmt_yuv(f.fmt) && (f.maxval != 255 || (fmt_yuv420(f.fmt) && mode_ != 420))) return kErrArg;
     if (gray && f.maxval != 255) return kErrArg;
+    // 10-bit layouts: 16-bit words, so an even base and even pitches
+    if (fmt_yuv10(f.fmt) && (((uintptr_t)f.rgb | f.stride | f.plane_stride) & 1)) return kErrArg;
     if (gray) qc = qy;
     const size_t row = (size_t)fmt_row_bytes(f.fmt, f.width);
     const size_t stride = f.stride ? f.stride : row;
@@ -710,10 +713,10 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     // (the packed 4:2:2 layouts are one plane of rows, NV16 two equal planes: the generic
     // copies; I422 has I420's chroma planes with a row per pixel row)
     const bool half = fmt_yuv420(f.fmt) || f.fmt == kFmtI422;
-    const size_t dev_pitch = align_up(row, f.fmt == kFmtI420 || f.fmt == kFmtI422 ? 32 : 16);
+    const size_t dev_pitch = align_up(row, f.fmt == kFmtI420 || f.fmt == kFmtI422 || f.fmt == kFmtI010 ? 32 : 16);
     const size_t dev_plane = dev_pitch * f.height;
     const size_t crows = f.fmt == kFmtI422 ? f.height : chroma_dim(f.height),
-                 crow = f.fmt == kFmtNv12 ? row : chroma_dim(f.width);  // (4:2:0 layouts, I422)
+                 crow = f.fmt == kFmtNv12 || f.fmt == kFmtP010 ? row : (size_t)fmt_bpp(f.fmt) * chroma_dim(f.width);  // (4:2:0 layouts, I422)
     const size_t cpitch = (size_t)fmt_chroma_pitch(f.fmt, stride), dev_cpitch = (size_t)fmt_chroma_pitch(f.fmt, dev_pitch);
     const size_t dev_bytes = half ? dev_plane + (planes - 1) * dev_cpitch * crows : planes * dev_plane;
     const bool dev_in = (flags & kFlagDeviceInput) != 0, dev_out = (flags & kFlagDeviceOutput) != 0;
@@ -732,7 +735,7 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
             JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, dev_bytes, hipMemcpyHostToDevice, s.stream));
         else if (half) {
             // the Y plane, then the chroma plane(s): NV12 one of Cb,Cr pairs, I420 Cb then Cr
-            JPGE_HIP(hipMemcpy2DAsync(s.d_in, dev_pitch, f.rgb, stride, (size_t)f.width, f.height, hipMemcpyHostToDevice,
+            JPGE_HIP(hipMemcpy2DAsync(s.d_in, dev_pitch, f.rgb, stride, (size_t)fmt_bpp(f.fmt) * f.width, f.height, hipMemcpyHostToDevice,
                                       s.stream));
             for (size_t c = 0; c + 1 < planes; ++c)
                 JPGE_HIP(hipMemcpy2DAsync(s.d_in + dev_plane + c * dev_cpitch * crows, dev_cpitch,

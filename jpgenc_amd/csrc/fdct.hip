@@ -172,7 +172,7 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
 #define JPGE_K1_SHAPE 0
 #endif
 constexpr int kShape = JPGE_K1_SHAPE;
-static_assert(kShape >= kShapeRgb8 && kShape <= kShapeI422, "JPGE_K1_SHAPE");
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapeI010, "JPGE_K1_SHAPE");
 // The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
 // layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
 // conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
@@ -183,7 +183,12 @@ static_assert(kShape >= kShapeRgb8 && kShape <= kShapeI422, "JPGE_K1_SHAPE");
 // instance only: 16 one-block MCUs per tile, the two Y rounds, no chroma rounds.
 constexpr bool kYuv = kShape >= kShapeNv12;
 constexpr bool kGray = kShape == kShapeGray;
-constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420;
+// The 10-bit 4:2:0 shapes (P010, I010) stage words s_y | s_cb<<10 | s_cr<<20 of 10-bit samples s,
+// each the exact fp64 value s / 4 in 8-bit units, and have the !kExact instances only: the
+// sample transform always runs (FULL_601: with the identity), because its clamps are what
+// keeps 1023 / 4 = 255.75 inside an 8-bit sample's interval.
+constexpr bool kTen = kShape == kShapeP010 || kShape == kShapeI010;
+constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420 || kTen;
 // The 4:2:2 shapes (YUYV / UYVY, NV16, I422) stage the same words, a cell's chroma sample in
 // both of its pixels (cell x >> 1 of the pixel's own row), and have every instance the planar
 // 4:4:4 shape has: each mode's filter then runs on the chroma-repeated frame.  In 4:2:2 the
@@ -192,7 +197,7 @@ constexpr bool kPacked422 = kShape == kShapePacked422;
 constexpr bool kPlanes422 = kShape == kShapeNv16 || kShape == kShapeI422;  // chroma loads of their own, row = pixel row
 constexpr bool kPairs = kShape == kShapeNv12 || kShape == kShapeNv16;      // Cb,Cr byte pairs
 constexpr bool kHalfPitch = kShape == kShapeI420 || kShape == kShapeI422;  // chroma pitch (stride + 1) / 2
-constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kPacked422 ? 2u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
+constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kPacked422 || kTen ? 2u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
 constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
 constexpr uint32_t kSelRgbx = 0x0C020100u, kSelBgrx = 0x0C000102u;  // perm selectors of a 4-byte pixel (0x0c: zero)
 
@@ -254,6 +259,27 @@ __device__ __forceinline__ void unpack_yuv420(const uint4& v0, const uint4& v1, 
         }
     }
 }
+// The 10-bit layouts' run: v0, v1 the 16 Y words, two per register.  P010 (a sample is its
+// word's top 10 bits): v2, v3 the 8 Cb,Cr word pairs of the run's cells, one per register.
+// I010 (the low 10 bits): v2 the cells' 8 Cb words, v3 their 8 Cr words.
+__device__ __forceinline__ void unpack_yuv10(const uint4& v0, const uint4& v1, const uint4& v2, const uint4& v3,
+                                             uint32_t px[16]) {
+    const uint32_t y[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    const uint32_t c[8] = {v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+    constexpr uint32_t lo = kShape == kShapeP010 ? 6u : 0u;  // the sample's first bit in its word
+#pragma unroll
+    for (int cell = 0; cell < 8; ++cell) {
+        uint32_t cc;  // s_cb << 10 | s_cr << 20
+        if constexpr (kShape == kShapeP010) {
+            cc = ((c[cell] << 4) & 0x000FFC00u) | ((c[cell] >> 2) & 0x3FF00000u);
+        } else {
+            const uint32_t sh = 16u * (uint32_t)(cell & 1);
+            cc = (__builtin_amdgcn_ubfe(c[cell >> 1], sh, 10u) << 10) | (__builtin_amdgcn_ubfe(c[4 + (cell >> 1)], sh, 10u) << 20);
+        }
+        px[2 * cell] = __builtin_amdgcn_ubfe(y[cell], lo, 10u) | cc;
+        px[2 * cell + 1] = __builtin_amdgcn_ubfe(y[cell], 16u + lo, 10u) | cc;
+    }
+}
 // The gray shape's run: the load's 16 bytes, one per staged word.
 __device__ __forceinline__ void unpack_gray(const uint4& v0, uint32_t px[16]) {
     const uint32_t y[4] = {v0.x, v0.y, v0.z, v0.w};
@@ -262,7 +288,11 @@ __device__ __forceinline__ void unpack_gray(const uint4& v0, uint32_t px[16]) {
 }
 // a staged word's samples (exact: integers)
 __device__ __forceinline__ double yuv_y(uint32_t p) { return (double)(p & 0xFF) - 128.0; }
-__device__ __forceinline__ double yuv_c(uint32_t p, int comp) { return (double)((p >> (8 * comp)) & 0xFF) - 128.0; }
+__device__ __forceinline__ double yuv_c(uint32_t p, int comp) {
+    // (10-bit fields: s / 4, exact)
+    if constexpr (kTen) return (double)((p >> (10 * comp)) & 0x3FF) * 0.25 - 128.0;
+    return (double)((p >> (8 * comp)) & 0xFF) - 128.0;
+}
 
 // The sample transform of the Y, Cb, Cr shapes' !kExact instances (host_io.hpp YuvXf: limited
 // range, BT.709 or the caller's coefficients): wave-uniform, held in scalar registers.  Every
@@ -276,7 +306,7 @@ struct XfK {
 __device__ __forceinline__ double xf_clamp_y(double s) { return __builtin_fmin(__builtin_fmax(s, 0.0), 255.0) - 128.0; }
 // Y' of a word's Y byte, given the products t1 = m1 u, t2 = m2 v of its chroma
 __device__ __forceinline__ double xf_y(const XfK& k, uint32_t p, double t1, double t2) {
-    const double yc = (double)(p & 0xFF) - k.y_off;
+    const double yc = kTen ? (double)(p & 0x3FF) * 0.25 - k.y_off : (double)(p & 0xFF) - k.y_off;  // (10-bit: s / 4, exact)
     if constexpr (kGray) return xf_clamp_y(k.m0 * yc);  // (one component: y_off and m0 only)
     return xf_clamp_y((k.m0 * yc + t1) + t2);
 }
@@ -306,6 +336,21 @@ __device__ __forceinline__ uint32_t edge_yuv(const uint8_t* base, uint64_t strid
         const uint8_t* p = base + (uint64_t)sy * stride + 4 * (uint64_t)(sx >> 1);
         const uint32_t w = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
         return __builtin_amdgcn_perm(0u, w, sel4 + 2u * (sx & 1));
+    }
+    if constexpr (kTen) {
+        // 16-bit little-endian words, by byte loads: P010 the word's top 10 bits, Cb,Cr word
+        // pairs in rows of pitch stride; I010 the low 10 bits, planes of pitch 2 * ceil(stride / 4)
+        auto word = [](const uint8_t* q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8); };
+        const uint8_t* c = base + plane_stride;
+        if constexpr (kShape == kShapeP010) {
+            c += (uint64_t)(sy >> 1) * stride + 4 * (uint64_t)(sx >> 1);
+            return (word(base + (uint64_t)sy * stride + 2 * (uint64_t)sx) >> 6) | ((word(c) >> 6) << 10) | ((word(c + 2) >> 6) << 20);
+        } else {
+            const uint64_t cs = 2 * ((stride + 3) / 4);
+            c += (uint64_t)(sy >> 1) * cs + 2 * (uint64_t)(sx >> 1);
+            return (word(base + (uint64_t)sy * stride + 2 * (uint64_t)sx) & 0x3FF) | ((word(c) & 0x3FF) << 10) |
+                   ((word(c + cs * ((gh + 1) / 2)) & 0x3FF) << 20);
+        }
     }
     const uint32_t yv = base[(uint64_t)sy * stride + sx];
     const uint8_t* c = base + plane_stride;
@@ -384,6 +429,19 @@ __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride,
     r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, (int)(uint32_t)(stride * (gh - 1) + 2 * (uint64_t)cw),
                                              0x00020000);
     r.p2 = r.p1;
+#elif JPGE_K1_SHAPE == 11
+    // the Cb,Cr plane: ch rows of pitch stride, cw pairs of 16-bit words each
+    const uint32_t cw = (gw + 1) / 2, ch = (gh + 1) / 2;
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, (int)(uint32_t)(stride * (ch - 1) + 4 * (uint64_t)cw),
+                                             0x00020000);
+    r.p2 = r.p1;
+#elif JPGE_K1_SHAPE == 12
+    // the Cb plane, then the Cr plane: ch rows of pitch cs, cw 16-bit words each
+    const uint32_t cw = (gw + 1) / 2, ch = (gh + 1) / 2;
+    const uint64_t cs = 2 * ((stride + 3) / 4);
+    const int crange = (int)(uint32_t)(cs * (ch - 1) + 2 * (uint64_t)cw);
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, crange, 0x00020000);
+    r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride + cs * ch, 0, crange, 0x00020000);
 #elif JPGE_K1_SHAPE == 10
     // the Cb plane, then the Cr plane: gh rows of pitch cs, cw bytes each
     const uint32_t cw = (gw + 1) / 2;
@@ -413,6 +471,13 @@ __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, coff, 0, 0));
 #elif JPGE_K1_SHAPE == 7
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+#elif JPGE_K1_SHAPE == 11 || JPGE_K1_SHAPE == 12
+    // 32 bytes of Y; P010: the 32 bytes of Cb,Cr pairs under them; I010: 16 bytes of each plane
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
+    v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff, 0, 0));
+    v3 = kShape == kShapeP010 ? as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff + 16, 0, 0))
+                              : as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, coff, 0, 0));
 #else
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
@@ -421,8 +486,13 @@ __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32
 #endif
 }
 
+#if JPGE_K1_SHAPE >= 11
+#define JPGE_K1_OCC __attribute__((amdgpu_waves_per_eu(4, 4)))
+#else
+#define JPGE_K1_OCC
+#endif
 template <bool kExact, int kWaves, int kFilt, int kN>
-__global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN> fs) {
+__global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<FdctArgs, kN> fs) {
     const uint32_t set_f = set_member<kN>(fs.wg0, fs.n, blockIdx.x);  // (frame sets: kernels.hpp)
     const FdctArgs& a = fs.a[set_f];
     const uint32_t bid = blockIdx.x - fs.wg0[set_f], nbk = fs.wg0[set_f + 1] - fs.wg0[set_f];
@@ -459,7 +529,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
     // (I420, I422: the chroma pitch, half the stride, is 16-byte aligned too)
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!kHalfPitch || (stride_ & 31) == 0);
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010) || (stride_ & 31) == 0);
     const int r16 = lane >> 2, c16 = lane & 3;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;     // DCT: lane -> (block of the round, column)
 
@@ -492,9 +562,15 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
     // 4:2:0 layouts: the chroma of the run's 8 cells, in chroma row (tile row * 8 + r16 / 2) of
     // pitch cpitch: NV12 the 16 bytes under the run, I420 the 16 bytes that hold its 8
     uint32_t cpitch = 0, lane_coff = 0;
-    if constexpr (kYuv420) {
+    if constexpr (kYuv420 && !kTen) {
         cpitch = kShape == kShapeNv12 ? (uint32_t)stride_ : (uint32_t)((stride_ + 1) / 2);
         lane_coff = (uint32_t)(r16 >> 1) * cpitch + (kShape == kShapeNv12 ? (uint32_t)c16 : (uint32_t)(c16 >> 1)) * 16;
+    }
+    // 10-bit: P010 the 32 bytes of pairs under the run, I010 the 16 bytes of each plane that are its 8 cells
+    constexpr uint32_t kCellRun = kShape == kShapeP010 ? 32u : 16u;  // chroma bytes (of one plane) of 8 cells
+    if constexpr (kTen) {
+        cpitch = kShape == kShapeP010 ? (uint32_t)stride_ : (uint32_t)(2 * ((stride_ + 3) / 4));
+        lane_coff = (uint32_t)(r16 >> 1) * cpitch + (uint32_t)c16 * kCellRun;
     }
     // NV16, I422: the same bytes of chroma row (tile row * 16 + r16), the pixels' own
     if constexpr (kPlanes422) {
@@ -512,8 +588,13 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         const uint32_t base = (uint32_t)((uint64_t)(mrow * 16) * stride_ + (uint64_t)mcol0 * kRun);  // (uniform)
         const uint32_t off = ok ? base + lane_off : kOob;
         uint32_t coff = kOob;
-        if constexpr (kYuv420) {
+        if constexpr (kYuv420 && !kTen) {
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kShape == kShapeNv12 ? 16 : 8));
+            coff = ok ? cbase + lane_coff : kOob;
+        }
+        if constexpr (kTen) {
+            // (I010: the run's 8 cells are the 16 bytes themselves, inside their row whenever the run is)
+            const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * kCellRun);
             coff = ok ? cbase + lane_coff : kOob;
         }
         if constexpr (kPlanes422) {
@@ -683,7 +764,9 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_kernel(FrameSet<FdctArgs, kN
         // (the prefetched registers are consumed on every path, so no later wait on
         // them can also drain the previous tile's coefficient stores)
         uint32_t px[16];
-        if constexpr (kYuv420 || kPlanes422) {
+        if constexpr (kTen) {
+            unpack_yuv10(c0, c1, c2, c3, px);
+        } else if constexpr (kYuv420 || kPlanes422) {
             unpack_yuv420(c0, c1, c2, (uint32_t)(c16 & 1), px);
         } else if constexpr (kPacked422) {
             unpack_packed422(c0, c1, sel4_, px);
@@ -835,7 +918,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
     // (I420, I422: the chroma pitch, half the stride, is 16-byte aligned too)
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!kHalfPitch || (stride_ & 31) == 0);
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010) || (stride_ & 31) == 0);
     const int r8 = lane >> 3, c8 = lane & 7;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;   // DCT: lane -> (block of the round, column)
 
@@ -1062,7 +1145,12 @@ static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hi
     const FdctArgs& a = fs.a[0];
     // (Y, Cb, Cr samples are 8-bit, maxval 255: their !kExact instances are the sample transform's)
     const bool ex = kYuv ? a.xf_on == 0 : a.maxval == 255;
-    if (k1_whole_cu(a.g, a.solo)) {
+    if constexpr (kTen) {
+        // 10-bit samples always go through the sample transform: no kExact instance
+        if (ex) return hipErrorInvalidValue;
+        if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+        return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+    } else if (k1_whole_cu(a.g, a.solo)) {
         if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         else return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
     } else {
@@ -1107,10 +1195,18 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
 
 #if JPGE_K1_SHAPE != 0
 // this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
-// _packed422 / _nv16 / _i422)
+// _packed422 / _nv16 / _i422 / _p010 / _i010)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
+#if JPGE_K1_SHAPE >= 11
+// the 10-bit shapes also have the lone frame's instance (launch_fdct_p010_one / _i010_one), as the RGB8 shape has
+#define JPGE_K1_CAT_(a, b) a##b
+#define JPGE_K1_CAT(a, b) JPGE_K1_CAT_(a, b)
+hipError_t JPGE_K1_CAT(JPGE_K1_ENTRY, _one)(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
+    return launch_k1<1>(fs, grid, s, t);
+}
+#endif
 #else
 hipError_t launch_fdct_bgr8(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_x4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
@@ -1122,6 +1218,10 @@ hipError_t launch_fdct_gray(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid
 hipError_t launch_fdct_packed422(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_nv16(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_i422(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_p010(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_i010(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_p010_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_i010_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 
 uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs) {
     const uint32_t tiles = k1_tiles(g);
@@ -1152,6 +1252,8 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
             return hipErrorInvalidValue;
         static_assert(kK1OffsetBound == kOob, "the host's bound is the kernel's out-of-range offset");
         if (!k1_offsets_fit(m.fmt, m.g, m.stride)) return hipErrorInvalidValue;
+        // 10-bit layouts: 16-bit words (even addresses and pitches), and always the sample transform
+        if (fmt_yuv10(m.fmt) && ((((uintptr_t)m.rgb | m.stride | m.plane_stride) & 1) || !m.xf_on)) return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
             fmt_shape(m.fmt) != fmt_shape(a.fmt) || (m.xf_on != 0) != (a.xf_on != 0) ||
             m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs))
@@ -1159,6 +1261,10 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
     }
     const uint32_t grid = fs.wg0[fs.n];
     if (fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
+    if constexpr (kN == 1) {
+        if (fmt_shape(a.fmt) == kShapeP010) return launch_fdct_p010_one(fs, grid, s, t);
+        if (fmt_shape(a.fmt) == kShapeI010) return launch_fdct_i010_one(fs, grid, s, t);
+    }
     // the other load shapes have the frame-set instance only (a lone frame is a set of one)
     FrameSet<FdctArgs, kMaxSet> w{};
     w.n = fs.n;
@@ -1174,6 +1280,8 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         case kShapePacked422: return launch_fdct_packed422(w, grid, s, t);
         case kShapeNv16: return launch_fdct_nv16(w, grid, s, t);
         case kShapeI422: return launch_fdct_i422(w, grid, s, t);
+        case kShapeP010: return launch_fdct_p010(w, grid, s, t);
+        case kShapeI010: return launch_fdct_i010(w, grid, s, t);
         default: return launch_fdct_planar(w, grid, s, t);
     }
 }

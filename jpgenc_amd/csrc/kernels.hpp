@@ -64,16 +64,21 @@ constexpr int kFmtNv12 = 16, kFmtI420 = 17, kFmtYuv444Planar = 18;
 // interleaved Cb,Cr rows), I422 (Y, Cb, Cr planes).  A frame is the planar 4:4:4 frame whose
 // chroma planes hold c[y][x >> 1] at pixel (y, x), in every subsampling mode.
 constexpr int kFmtYuyv = 20, kFmtUyvy = 21, kFmtNv16 = 22, kFmtI422 = 23;
+// 10-bit 4:2:0 frames of little-endian 16-bit words: P010 (NV12's planes, a sample in the top 10
+// bits of its word) and I010 (I420's planes, a sample in the low 10 bits).  A sample s is the
+// exact fp64 value s / 4 in 8-bit units, and always goes through the sample transform.
+constexpr int kFmtP010 = 32, kFmtI010 = 33;
 // one plane of 8-bit luminance samples (a sample v is the fp64 value v - 128, as a Y sample
 // above): a one-component stream, Geometry::gray(), whatever the subsampling mode
 constexpr int kFmtGray8 = 8;
 JPGE_HD inline bool fmt_valid(int fmt) {
     return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar) ||
-           (fmt >= kFmtYuyv && fmt <= kFmtI422);
+           (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt == kFmtP010 || fmt == kFmtI010;
 }
 JPGE_HD inline bool fmt_gray(int fmt) { return fmt == kFmtGray8; }
 JPGE_HD inline bool fmt_yuv(int fmt) { return fmt >= kFmtNv12; }
-JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420; }  // chroma planes at half size
+JPGE_HD inline bool fmt_yuv10(int fmt) { return fmt == kFmtP010 || fmt == kFmtI010; }  // 16-bit words of 10-bit samples
+JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420 || fmt_yuv10(fmt); }  // chroma planes at half size
 JPGE_HD inline bool fmt_yuv422(int fmt) { return fmt >= kFmtYuyv && fmt <= kFmtI422; }  // chroma at half width, every row
 JPGE_HD inline bool fmt_packed422(int fmt) { return fmt == kFmtYuyv || fmt == kFmtUyvy; }
 constexpr int kShapeRgb8 = 0;    // 48 bytes R,G,B,...: three b128 loads
@@ -87,25 +92,31 @@ constexpr int kShapeGray = 7;    // 16 Y bytes: one b128 load (no chroma: Geomet
 constexpr int kShapePacked422 = 8;  // YUYV / UYVY: the run's 32 bytes, two b128 loads, wave-uniform byte selectors
 constexpr int kShapeNv16 = 9;    // the NV12 shape's two loads, the Cb,Cr row that of the pixels
 constexpr int kShapeI422 = 10;   // the I420 shape's three loads, the chroma rows those of the pixels
+constexpr int kShapeP010 = 11;   // 32 Y bytes (16 words) + the 32 bytes of Cb,Cr word pairs under them: four b128 loads
+constexpr int kShapeI010 = 12;   // 32 Y bytes + the 16 Cb bytes + the 16 Cr bytes of the run's 8 cells: four b128 loads
 JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
+    return fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
          : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
 }
 // bytes per pixel within a row (planar: of one plane), and planes
-JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt_packed422(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
-JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
+JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt_packed422(fmt) || fmt_yuv10(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
+JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 || fmt == kFmtP010 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
 // The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
 // that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs; NV16 likewise; the packed
 // 4:2:2 layouts: ceil(width / 2) whole 4-byte groups).
 JPGE_HD inline uint64_t fmt_row_bytes(int fmt, uint32_t width) {
     if (fmt_packed422(fmt)) return 4 * (((uint64_t)width + 1) / 2);
+    if (fmt == kFmtP010) return 2 * (((uint64_t)width + 1) & ~(uint64_t)1);  // (16-bit words; I010: 2 * width, by fmt_bpp)
     return fmt == kFmtNv12 || fmt == kFmtNv16 ? ((uint64_t)width + 1) & ~(uint64_t)1 : (uint64_t)fmt_bpp(fmt) * width;
 }
 // The 4:2:0 layouts' chroma: ceil(height / 2) rows of ceil(width / 2) samples, starting
 // plane_stride bytes after the Y plane; row pitch `stride` (NV12, 2 bytes per sample) or
 // (stride + 1) / 2 (I420, whose Cr plane follows the Cb plane's rows).  NV16 and I422: the
 // same pitches and order, `height` rows of ceil(width / 2) samples.
-JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) { return fmt == kFmtI420 || fmt == kFmtI422 ? (stride + 1) / 2 : stride; }
+// I010: 2 * ceil(stride / 4), whole 16-bit words; P010: stride.
+JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) {
+    return fmt == kFmtI010 ? 2 * ((stride + 3) / 4) : fmt == kFmtI420 || fmt == kFmtI422 ? (stride + 1) / 2 : stride;
+}
 JPGE_HD inline uint32_t chroma_dim(uint32_t n) { return (n + 1) / 2; }
 // The transform kernel reaches a frame's pixels and its coefficients through 32-bit buffer
 // offsets: stride * height (planar layouts: of one plane; each plane has a descriptor of its

@@ -324,6 +324,47 @@ int jpge_get_yuv_transform(jpge_ctx* ctx, int* preset, jpge_yuv_transform* t);
  * JPGE_YUV_CUSTOM and unknown presets.  (An addition.) */
 int jpge_yuv_preset(int preset, jpge_yuv_transform* t);
 
+/* ---- Box downscale of the input (an addition; replaces nothing in the reference) ----
+ * With factor s = 2 or 4 a width x height frame is coded at dw = ceil(width / s),
+ * dh = ceil(height / s): the transform kernel averages s x s source samples into each
+ * sample it reads, so a 4K or 8K surface becomes a 1080p .jpg without a resize pass and
+ * without a second surface.  Every 8-bit sample of the downscaled frame D is the integer
+ * mean, rounded half up, of its source samples, their coordinates clamped to the plane:
+ *
+ *   D[y][x][c] = (sum_{j<s, i<s} S[min(s*y + j, H-1)][min(s*x + i, W-1)][c] + s*s/2) / (s*s)
+ *
+ * NV12: the Y plane over width x height, and the Cb,Cr plane the same way in its own
+ * domain (ceil(width / 2) x ceil(height / 2), Cb and Cr separately).  RGBA8 / BGRA8: alpha
+ * is ignored.  The .jpg of a frame coded with factor s is, byte for byte, the .jpg of D
+ * (jpge_downscale_frame) coded with factor 1 in the same layout, under every other
+ * setting; SOF0 carries dw x dh.
+ *
+ * The factor applies to the context's following jpge_encode_rgb8, jpge_encode_batch,
+ * jpge_encode_file(s), jpge_fdct_quant and jpge_symbol_stats calls (the last two return
+ * D's planes and histograms), and on a group member's context to jpge_group_encode_batch.
+ * Layouts with s > 1: JPGE_FMT_RGB8, _BGR8, _RGBA8, _BGRA8 in every subsampling mode and
+ * JPGE_FMT_NV12; with any other layout those calls return JPGE_E_ARG (a batch: the frame's
+ * status) before anything is queued, as do jpge_stripe_transform and
+ * jpge_group_encode_striped.  jpge_encode_planes and the plane stages ignore the setting.
+ * The limits on width, height and stride are the source's; jpge_max_jpeg_bytes(dw, dh)
+ * bounds the output.
+ *
+ * 1 (the default), 2 or 4; anything else, or a NULL context: JPGE_E_ARG, the setting
+ * unchanged. */
+int jpge_set_downscale(jpge_ctx* ctx, int factor);
+int jpge_get_downscale(jpge_ctx* ctx, int* factor);
+/* dw, dh of a width x height frame; host only.  JPGE_E_ARG: a factor other than 1, 2, 4,
+ * a zero dimension or a NULL pointer. */
+int jpge_downscaled_size(uint32_t width, uint32_t height, int factor, uint32_t* dw, uint32_t* dh);
+/* The rule above in plain C++, host only: src (width x height in `format`, row pitch
+ * stride, 0 = dense; NV12: the Cb,Cr plane plane_stride bytes after the Y plane, 0 =
+ * stride * height) to dst (dw x dh in the same layout, dst_stride and dst_plane_stride
+ * likewise).  Factor 1 copies the rows; with 2 or 4 a 4-byte layout's fourth byte is 255.
+ * JPGE_E_ARG: a layout without a downscaling kernel, another factor, a zero dimension, a
+ * NULL pointer, a stride below a row's bytes or a plane stride below the Y plane's. */
+int jpge_downscale_frame(int format, const uint8_t* src, uint32_t width, uint32_t height, size_t stride,
+                         size_t plane_stride, int factor, uint8_t* dst, size_t dst_stride, size_t dst_plane_stride);
+
 /* Worst-case .jpg size for a frame, in any subsampling mode (header + 2x
  * worst-case entropy + RST markers + EOI). */
 size_t jpge_max_jpeg_bytes(uint32_t width, uint32_t height);

@@ -69,6 +69,7 @@ EXPORTS = (
     "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info",
     "jpge_set_huffman", "jpge_get_huffman", "jpge_standard_huffman",
     "jpge_set_yuv_transform", "jpge_get_yuv_transform", "jpge_yuv_preset",
+    "jpge_set_downscale", "jpge_get_downscale", "jpge_downscaled_size", "jpge_downscale_frame",
     "jpge_max_jpeg_bytes", "jpge_quality_tables", "jpge_encode_rgb8", "jpge_encode_batch",
     "jpge_fdct_quant", "jpge_symbol_stats", "jpge_huffman_table", "jpge_huffman_text", "jpge_parse_ppm",
     "jpge_ppm_info", "jpge_encode_file", "jpge_encode_files", "jpge_synth_rgb8", "jpge_arai_constants",
@@ -212,6 +213,10 @@ def lib() -> ctypes.CDLL:
         L.jpge_set_yuv_transform.argtypes = [vp, i32, ctypes.POINTER(YuvTransform)]
         L.jpge_get_yuv_transform.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(YuvTransform)]
         L.jpge_yuv_preset.argtypes = [i32, ctypes.POINTER(YuvTransform)]
+        L.jpge_set_downscale.argtypes = [vp, i32]
+        L.jpge_get_downscale.argtypes = [vp, ctypes.POINTER(i32)]
+        L.jpge_downscaled_size.argtypes = [u32, u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.jpge_downscale_frame.argtypes = [i32, vp, u32, u32, sz, sz, i32, vp, sz, sz]
         L.jpge_device_count.argtypes = [ctypes.POINTER(i32)]
         L.jpge_max_jpeg_bytes.restype = sz
         L.jpge_max_jpeg_bytes.argtypes = [u32, u32]
@@ -713,6 +718,34 @@ def _as_frames(frames, fmt: int):
     return [f[0] for f in fr], [f[1:] for f in fr]
 
 
+def downscaled_size(w: int, h: int, s: int) -> tuple[int, int]:
+    """(ceil(w / s), ceil(h / s)) for s = 1, 2 or 4 (jpge_downscaled_size)."""
+    dw, dh = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().jpge_downscaled_size(int(w), int(h), int(s), ctypes.byref(dw), ctypes.byref(dh)), "downscaled_size")
+    return dw.value, dh.value
+
+
+def downscale_frame(a, fmt: int, s: int):
+    """The frame an encode with Encoder.set_downscale(s) codes (jpge_downscale_frame, on the
+    host): `a` shaped for layout `fmt` (RGB8, BGR8, RGBA8, BGRA8: (H, W, C); NV12: a
+    pack_yuv420 frame) -> the frame of ceil(W / s) x ceil(H / s) pixels in the same layout,
+    every sample the mean, rounded half up, of its s x s source samples."""
+    a, w, h, stride = _as_frame(a, fmt)
+    dw, dh = downscaled_size(w, h, s)
+    if fmt == JPGE_FMT_NV12:
+        dstride = 2 * ((dw + 1) // 2)
+        out = np.zeros(yuv420_bytes(fmt, dw, dh), np.uint8)
+    else:
+        bpp = input_format_info(fmt)[0]
+        dstride = dw * bpp
+        out = np.zeros((dh, dw, bpp), np.uint8)
+    _check(lib().jpge_downscale_frame(int(fmt), _p(a), w, h, stride, 0, int(s), _p(out), dstride, 0), "downscale_frame")
+    if fmt == JPGE_FMT_NV12:
+        out = out.view(Yuv420Frame)
+        out.fmt, out.width, out.height, out.stride = int(fmt), dw, dh, dstride
+    return out
+
+
 def device_count() -> int:
     n = ctypes.c_int(0)
     lib().jpge_device_count(ctypes.byref(n))
@@ -846,6 +879,21 @@ class Encoder:
         p, t = ctypes.c_int32(), YuvTransform()
         _check(lib().jpge_get_yuv_transform(self._ctx, ctypes.byref(p), ctypes.byref(t)), "get_yuv_transform")
         return p.value, t.as_tuple()
+
+    def set_downscale(self, factor: int) -> None:
+        """Box downscale of the following encodes (encode*, encode_tensor, encode_tensor_yuv with
+        NV12, encode_batch, encode_file(s), fdct_quant, symbol_stats): 1 (none), 2 or 4.  A W x H
+        frame is coded at ceil(W / factor) x ceil(H / factor), each sample the rounded mean of
+        factor x factor source samples, averaged inside the transform kernel: the bytes are
+        those of encoding downscale_frame(frame, fmt, factor).  RGB8, BGR8, RGBA8, BGRA8 and
+        NV12 input; other layouts and the stripe phases fail with JPGE_E_ARG while it is set."""
+        _check(lib().jpge_set_downscale(self._ctx, int(factor)), "set_downscale")
+
+    @property
+    def downscale(self) -> int:
+        f = ctypes.c_int32()
+        _check(lib().jpge_get_downscale(self._ctx, ctypes.byref(f)), "get_downscale")
+        return f.value
 
     def lanes(self) -> int:
         n = ctypes.c_int32()
@@ -1259,7 +1307,8 @@ class Encoder:
                                          None, 0), "fdct_quant")
             return y, None, None
         yh, yv = SUBSAMPLING[getattr(self, "_sub", 420)]
-        mw, mh = -(-w // (8 * yh)), -(-h // (8 * yv))  # MCUs across / down
+        dw, dh = downscaled_size(w, h, self.downscale)  # (the coded frame's blocks)
+        mw, mh = -(-dw // (8 * yh)), -(-dh // (8 * yv))  # MCUs across / down
         y = np.zeros((mw * yh * mh * yv, 64), np.int16)
         cb = np.zeros((mw * mh, 64), np.int16)
         cr = np.zeros_like(cb)
@@ -1434,6 +1483,14 @@ class Group:
             c = ctypes.c_void_p()
             _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
             _check(lib().jpge_set_yuv_transform(c, int(preset), t), "set_yuv_transform")
+
+    def set_downscale(self, factor: int) -> None:
+        """Box downscale of every member's context (Encoder.set_downscale): for encode_batch;
+        encode_striped needs factor 1."""
+        for m in range(self.size()[0]):
+            c = ctypes.c_void_p()
+            _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
+            _check(lib().jpge_set_downscale(c, int(factor)), "set_downscale")
 
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         """Config 4: frame i on member i mod N."""

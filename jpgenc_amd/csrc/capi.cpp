@@ -322,6 +322,76 @@ int jpge_yuv_preset(int preset, jpge_yuv_transform* t) {
     return JPGE_OK;
 }
 
+int jpge_set_downscale(jpge_ctx* ctx, int factor) {
+    CtxUse use(ctx);
+    if (!use) return JPGE_E_ARG;
+    return ctx->enc->set_downscale(factor) ? JPGE_E_ARG : JPGE_OK;
+}
+
+int jpge_get_downscale(jpge_ctx* ctx, int* factor) {
+    CtxUse use(ctx);
+    if (!use || !factor) return JPGE_E_ARG;
+    *factor = ctx->enc->downscale();
+    return JPGE_OK;
+}
+
+int jpge_downscaled_size(uint32_t w, uint32_t h, int factor, uint32_t* dw, uint32_t* dh) {
+    if (!jpge::ds_valid(factor) || !w || !h || !dw || !dh) return JPGE_E_ARG;
+    *dw = jpge::ds_dim(w, factor);
+    *dh = jpge::ds_dim(h, factor);
+    return JPGE_OK;
+}
+
+namespace {
+// One plane of `ch` interleaved channels (`step` bytes from a pixel to the next): the rounded
+// means of s x s clamped source samples (jpge.h, jpge_set_downscale).
+void box_plane(const uint8_t* src, uint32_t w, uint32_t h, size_t stride, int step, int ch, int s, uint8_t* dst,
+               size_t dst_stride) {
+    const uint32_t dw = jpge::ds_dim(w, s), dh = jpge::ds_dim(h, s);
+    const uint32_t n = (uint32_t)(s * s);
+    for (uint32_t y = 0; y < dh; ++y)
+        for (uint32_t x = 0; x < dw; ++x)
+            for (int c = 0; c < ch; ++c) {
+                uint32_t sum = 0;
+                for (uint32_t j = 0; j < (uint32_t)s; ++j)
+                    for (uint32_t i = 0; i < (uint32_t)s; ++i)
+                        sum += src[(size_t)std::min(s * y + j, h - 1) * stride + (size_t)std::min(s * x + i, w - 1) * step + c];
+                dst[(size_t)y * dst_stride + (size_t)x * step + c] = (uint8_t)((sum + n / 2) / n);
+            }
+}
+}  // namespace
+
+int jpge_downscale_frame(int format, const uint8_t* src, uint32_t w, uint32_t h, size_t stride, size_t plane_stride,
+                         int s, uint8_t* dst, size_t dst_stride, size_t dst_plane_stride) {
+    if (!jpge::ds_valid(s) || !jpge::ds_fmt(format) || !src || !dst || !w || !h) return JPGE_E_ARG;
+    const uint32_t dw = jpge::ds_dim(w, s), dh = jpge::ds_dim(h, s);
+    const size_t row = (size_t)jpge::fmt_row_bytes(format, w), drow = (size_t)jpge::fmt_row_bytes(format, dw);
+    if (!stride) stride = row;
+    if (!dst_stride) dst_stride = drow;
+    if (stride < row || dst_stride < drow) return JPGE_E_ARG;
+    if (format == JPGE_FMT_NV12) {
+        if (!plane_stride) plane_stride = stride * h;
+        if (!dst_plane_stride) dst_plane_stride = dst_stride * dh;
+        if (plane_stride < stride * (h - 1) + row || dst_plane_stride < dst_stride * (dh - 1) + drow) return JPGE_E_ARG;
+        box_plane(src, w, h, stride, 1, 1, s, dst, dst_stride);
+        // the Cb,Cr plane in its own domain: ceil(w / 2) x ceil(h / 2) pairs to ceil(dw / 2) x ceil(dh / 2)
+        box_plane(src + plane_stride, jpge::chroma_dim(w), jpge::chroma_dim(h), stride, 2, 2, s, dst + dst_plane_stride,
+                  dst_stride);
+        return JPGE_OK;
+    }
+    if (plane_stride || dst_plane_stride) return JPGE_E_ARG;  // (one plane)
+    const int bpp = (int)jpge::fmt_bpp(format);
+    if (s == 1) {
+        for (uint32_t y = 0; y < h; ++y) std::memcpy(dst + (size_t)y * dst_stride, src + (size_t)y * stride, row);
+        return JPGE_OK;
+    }
+    box_plane(src, w, h, stride, bpp, 3, s, dst, dst_stride);
+    if (bpp == 4)  // (alpha is ignored: opaque)
+        for (uint32_t y = 0; y < dh; ++y)
+            for (uint32_t x = 0; x < dw; ++x) dst[(size_t)y * dst_stride + (size_t)x * 4 + 3] = 255;
+    return JPGE_OK;
+}
+
 int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes) {
     if (!jpge::fmt_valid(format)) return JPGE_E_ARG;
     if (bytes_per_pixel) *bytes_per_pixel = (int)jpge::fmt_bpp(format);

@@ -8,7 +8,10 @@
 //   --restart M                    restart interval in MCUs (DRI/RSTn);
 //   --huffman optimal|standard     per-image Huffman tables (the default, the reference's
 //                                  stream) or the ITU T.81 Annex K tables
-//                                  (jpge_set_huffman; not with --gpus / --devices).
+//                                  (jpge_set_huffman; not with --gpus / --devices);
+//   --downscale 2|4                code the image at 1/2 or 1/4 size, each sample the mean of
+//                                  2x2 or 4x4 source samples (jpge_set_downscale; not with
+//                                  --gpus / --devices).
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -54,6 +57,7 @@ int main(int argc, char* argv[]) {
     int quality = 50;
     uint32_t restart = 0;
     int huffman = JPGE_HUFF_OPTIMAL;
+    int downscale = 1;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-q") && i + 1 < argc) {
             quality = std::atoi(argv[++i]);
@@ -76,6 +80,12 @@ int main(int argc, char* argv[]) {
                 std::cerr << "jpgenc: --huffman takes optimal or standard" << std::endl;
                 return 1;
             }
+        } else if (!std::strcmp(argv[i], "--downscale") && i + 1 < argc) {
+            downscale = std::atoi(argv[++i]);
+            if (downscale != 1 && downscale != 2 && downscale != 4) {
+                std::cerr << "jpgenc: --downscale takes 1, 2 or 4" << std::endl;
+                return 1;
+            }
         } else {
             pos.emplace_back(argv[i]);
         }
@@ -88,11 +98,13 @@ int main(int argc, char* argv[]) {
     try {
         if (!devs.empty()) {
             if (huffman != JPGE_HUFF_OPTIMAL) throw std::runtime_error("--huffman standard: not for striped encodes");
+            if (downscale != 1) throw std::runtime_error("--downscale: not for striped encodes");
             return striped(devs, pos[0], jpg, quality, restart);
         }
         auto img = jpge::loadPPM(pos[0]);
         if (restart) jpge::detail::check(jpge_set_restart_interval(jpge::default_context(), restart), "restart");
         if (huffman) jpge::detail::check(jpge_set_huffman(jpge::default_context(), huffman, nullptr), "huffman");
+        if (downscale != 1) jpge::detail::check(jpge_set_downscale(jpge::default_context(), downscale), "downscale");
         img.writeJPEG(jpg, quality);
     } catch (const std::exception& e) {
         std::cerr << "jpgenc: " << e.what() << std::endl;

@@ -287,6 +287,18 @@ int Encoder::set_input_format(int fmt, size_t plane_stride) {
     return kOk;
 }
 
+int Encoder::set_downscale(int factor) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    if (!ds_valid(factor)) return kErrArg;
+    ds_ = factor;
+    return kOk;
+}
+
+int Encoder::downscale() {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    return ds_;
+}
+
 int Encoder::set_yuv_transform(int preset, const YuvXf* custom) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     YuvXf t;
@@ -599,6 +611,9 @@ FdctArgs Encoder::fdct_args(Slot& s, int maxval, Slot* imp) {
     a.stride = s.in_stride;
     a.fmt = s.in_fmt;
     a.plane_stride = s.in_plane_stride;
+    a.ds = (uint32_t)s.ds;
+    a.src_w = s.src_w;
+    a.src_h = s.src_h;
     // the sample transform of Y, Cb, Cr and gray frames (FULL_601: the kExact instances)
     // (10-bit samples always: FULL_601 runs it with the identity, for its clamps)
     a.xf_on = ((fmt_yuv(s.in_fmt) || fmt_gray(s.in_fmt)) && yuv_preset_ != kYuvFull601) || fmt_yuv10(s.in_fmt) ? 1u : 0u;
@@ -695,7 +710,15 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     if (f.maxval < 1 || f.maxval > 255) return kErrRange;
     // (one component: no chroma, so the subsampling mode does not enter, and qc is not read)
     const bool gray = fmt_gray(f.fmt);
-    const Geometry g = gray ? gray_geometry(f.width, f.height) : geometry(f.width, f.height, mode_);
+    // a downscaled frame: f is the source (its limits, pitches and upload are the source's), and
+    // the geometry of everything K1 writes is that of the frame of ceil(f / ds) pixels
+    const int ds = ds_;
+    if (ds > 1 && !ds_fmt(f.fmt)) return kErrArg;  // (the layouts without a downscaling kernel)
+    const uint32_t out_w = ds_dim(f.width, ds), out_h = ds_dim(f.height, ds);
+    const Geometry g = gray ? gray_geometry(out_w, out_h) : geometry(out_w, out_h, mode_);
+    Geometry src = g;  // (the extent K1's offsets span)
+    src.width = f.width;
+    src.height = f.height;
     if (!fmt_valid(f.fmt) || (f.plane_stride && fmt_planes(f.fmt) == 1)) return kErrArg;
     // Y, Cb, Cr samples are 8-bit, and half-size chroma planes are the S420_m mode's planes
     if (fmt_yuv(f.fmt) && (f.maxval != 255 || (fmt_yuv420(f.fmt) && mode_ != 420))) return kErrArg;
@@ -722,9 +745,9 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     const bool dev_in = (flags & kFlagDeviceInput) != 0, dev_out = (flags & kFlagDeviceOutput) != 0;
     // the kernel's 32-bit offsets must span the frame it reads (a device frame in place at its
     // own pitch, a host frame's copy): refused here, before a slot grows or anything is queued
-    if (!k1_offsets_fit(f.fmt, g, dev_in ? stride : dev_pitch)) return kErrArg;
+    if (!k1_offsets_fit(f.fmt, src, dev_in ? stride : dev_pitch)) return kErrArg;
     const size_t in_bytes = dev_in ? 0 : dev_bytes;
-    const size_t out_cap = dev_out ? 0 : max_jpeg_bytes(f.width, f.height);
+    const size_t out_cap = dev_out ? 0 : max_jpeg_bytes(out_w, out_h);
     if (!tables_nonzero(qy, qc)) return kErrArg;
     const int st0 = ensure(s, g, in_bytes, out_cap);
     if (st0) return st0;
@@ -748,7 +771,7 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     }
     s.begin(g, qy, qc, dev_in ? f.rgb : s.d_in, dev_in ? stride : dev_pitch, f.fmt,
             planes > 1 ? (dev_in ? plane_stride : dev_plane) : 0, dev_out ? f.out : s.d_out,
-            dev_out ? f.cap : s.cap_out, restart_mcus_, f.width, f.height);
+            dev_out ? f.cap : s.cap_out, restart_mcus_, out_w, out_h, ds, ds > 1 ? f.width : 0, ds > 1 ? f.height : 0);
     if (flags & kFlagFixedTables) {
         // fixed Huffman tables: the frame's own transform kernel carries its code words and
         // headers to the device, where they are new there
@@ -1050,7 +1073,7 @@ int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], ui
     // kFirstSleepMaxPixels: the helper spins from here to the histograms, which take
     // milliseconds there, for tables that are a small part of such a call.
     TableHelper* helper = nullptr;
-    const uint64_t npx = (uint64_t)f.width * f.height;
+    const uint64_t npx = (uint64_t)ds_dim(f.width, ds_) * ds_dim(f.height, ds_);  // (the coded frame's)
     if (!st && table_helper_ && lanes_.size() == 1 && npx >= (1u << 20) && npx <= kFirstSleepMaxPixels) {
         if (!helper_) helper_.reset(new TableHelper());
         helper = helper_.get();
@@ -1194,10 +1217,13 @@ int Encoder::batch_set_size(const FrameDesc* fr, int n) const {
             fr[i].fmt != f0.fmt)
             return 1;
     const bool placed_in_code = (ext_place_ > 0 || (ext_place_ < 0 && lanes_.size() > 1)) && place_in_code_;
-    const Geometry g0 = fmt_gray(f0.fmt) ? gray_geometry(f0.width, f0.height) : geometry(f0.width, f0.height, mode_);
+    // (downscaled frames: one source size and one factor give one output geometry, which is
+    // the one the kernels after K1 and the set's size go by)
+    const uint32_t w0 = ds_dim(f0.width, ds_), h0 = ds_dim(f0.height, ds_);
+    const Geometry g0 = fmt_gray(f0.fmt) ? gray_geometry(w0, h0) : geometry(w0, h0, mode_);
     if (!placed_in_code || restart_mcus_ || layout(g0).grid() > kPlaceInCodeMaxWgs) return 1;
     if (set_) return set_;
-    const uint64_t k = kSetPixels / ((uint64_t)f0.width * f0.height);
+    const uint64_t k = kSetPixels / ((uint64_t)w0 * h0);
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(kMaxSet, k));
 }
 

@@ -155,6 +155,13 @@ class Encoder {
     int set_yuv_transform(int preset, const YuvXf* custom);
     void yuv_transform(int* preset, YuvXf* t);
 
+    // Box downscale of the following pixel encodes and stage entries (jpge.h jpge_set_downscale):
+    // 1 (none), 2 or 4.  With a factor above 1 K1 averages factor x factor source samples into
+    // each sample it stages; the RGB8, BGR8, RGBA8, BGRA8 and NV12 layouts have such kernels, the
+    // other layouts and the stripe phases refuse the factor.  encode_planes ignores it.
+    int set_downscale(int factor);
+    int downscale();
+
     int lanes() const { return (int)lanes_.size(); }
 
   private:
@@ -230,6 +237,7 @@ class Encoder {
     uint32_t restart_mcus_ = 0; // restart interval (jpge_set_restart_interval)
     int mode_ = 420;            // subsampling mode (jpge_set_subsampling)
     int fmt_ = kFmtRgb8;        // input layout (jpge_set_input_format)
+    int ds_ = 1;                // box downscale factor (jpge_set_downscale)
     // Huffman mode (jpge_set_huffman) and, in a fixed mode, the four tables: as given, as
     // codes, and as the [4][256] (len << 16) | code words the code kernel reads (built once,
     // at set_huffman); the generation numbers a setting (a slot remembers whose tables it holds)

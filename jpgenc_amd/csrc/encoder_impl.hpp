@@ -156,6 +156,10 @@ struct Encoder::Slot {
     size_t in_stride = 0;
     int in_fmt = kFmtRgb8;         // the input's layout (kernels.hpp kFmt*)
     size_t in_plane_stride = 0;
+    // box downscale (jpge_set_downscale): ds > 1: the input is a src_w x src_h frame at in_stride,
+    // and g, img_w, img_h and everything after K1 are the frame of ceil(src / ds) pixels
+    int ds = 1;
+    uint32_t src_w = 0, src_h = 0;
     uint8_t* out_dev = nullptr;
     size_t out_cap = 0;
     size_t hdr_len = 0;
@@ -201,7 +205,11 @@ struct Encoder::Slot {
     // MCU the image's, untimed until phase 1 says otherwise.  A stripe then sets its
     // keys and rst.mcu0.  (img_w, img_h: the header's dimensions.)
     void begin(const Geometry& geo, const uint8_t y[64], const uint8_t c[64], const uint8_t* in, size_t stride, int fmt,
-               size_t plane_stride, uint8_t* out, size_t cap, uint32_t restart, uint32_t w, uint32_t h) {
+               size_t plane_stride, uint8_t* out, size_t cap, uint32_t restart, uint32_t w, uint32_t h, int factor = 1,
+               uint32_t source_w = 0, uint32_t source_h = 0) {
+        ds = factor;
+        src_w = source_w;
+        src_h = source_h;
         std::memcpy(qy, y, 64);
         std::memcpy(qc, c, 64);
         g = geo;

@@ -199,6 +199,17 @@ constexpr bool kPairs = kShape == kShapeNv12 || kShape == kShapeNv16;      // Cb
 constexpr bool kHalfPitch = kShape == kShapeI420 || kShape == kShapeI422;  // chroma pitch (stride + 1) / 2
 constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kPacked422 || kTen ? 2u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
 constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
+// The downscaling builds (JPGE_K1_DS 2 or 4; FdctArgs::ds) of the RGB8, BGR8, 4-byte and NV12
+// shapes: a staged word holds the rounded means of kDs x kDs source samples, so the lane's run
+// comes from 16 * kDs source pixels on kDs rows ("downscaling loads" below).  The tile, the
+// staged words and everything after the staging are those of the frame of ceil(src / kDs) pixels.
+#ifndef JPGE_K1_DS
+#define JPGE_K1_DS 1
+#endif
+constexpr int kDs = JPGE_K1_DS;
+static_assert(kDs == 1 || ((kDs == 2 || kDs == 4) && (kShape <= kShapeX4 || kShape == kShapeNv12)), "JPGE_K1_DS");
+constexpr uint32_t kDsBits = kDs == 4 ? 4u : kDs == 2 ? 2u : 0u;  // log2 of the samples of a mean
+constexpr uint32_t kDsHalf = (1u << kDsBits) >> 1;                // round half up
 constexpr uint32_t kSelRgbx = 0x0C020100u, kSelBgrx = 0x0C000102u;  // perm selectors of a 4-byte pixel (0x0c: zero)
 
 // perm selector of a 3-byte pixel starting at byte o8 of a word pair
@@ -486,6 +497,170 @@ __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32
 #endif
 }
 
+// ---- downscaling loads (kDs > 1) ----
+// A lane's run is 16 output pixels of one output row: kDs units of 16 / kDs pixels, each unit
+// the kRun source bytes under it on kDs source rows, loaded as the shape's b128 loads of one
+// row at a time and reduced as they arrive, so that a few unit rows of raw bytes (ds_pipeline)
+// and one unit's sums are live at once.  A sum is at most 16 * 255: each is a 32-bit accumulator of
+// v_dot4_u32_u8 with a constant byte mask, one per word the sample's bytes of that row touch.
+//
+// acc + the n bytes first, first + step, ... of a unit row's words w (all compile-time
+// after unrolling: the masks are constants, and a word without a byte costs nothing)
+template <int kW>
+__device__ __forceinline__ uint32_t add_bytes(const uint32_t (&w)[kW], int first, int step, int n, uint32_t acc) {
+#pragma unroll
+    for (int d = 0; d < kW; ++d) {
+        uint32_t m = 0;
+#pragma unroll
+        for (int t = 0; t < n; ++t)
+            if (((first + t * step) >> 2) == d) m |= 1u << (8 * ((first + t * step) & 3));
+        if (m) acc = __builtin_amdgcn_udot4(w[d], m, acc, false);
+    }
+    return acc;
+}
+// kN b128 loads at off, off + 16, ... as words (kOob + 48 is still past every range)
+template <int kN>
+__device__ __forceinline__ void load_words(__amdgpu_buffer_rsrc_t rs, uint32_t off, uint32_t (&w)[4 * kN]) {
+#pragma unroll
+    for (int q = 0; q < kN; ++q) {
+        const uint4 v = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs, off + 16u * (uint32_t)q, 0, 0));
+        w[4 * q] = v.x;
+        w[4 * q + 1] = v.y;
+        w[4 * q + 2] = v.z;
+        w[4 * q + 3] = v.w;
+    }
+}
+__device__ __forceinline__ uint32_t ds_mean(uint32_t sum) { return (sum + kDsHalf) >> kDsBits; }
+// A step's sums are pinned where they are computed: they are pure arithmetic whose results the
+// next tile's staging uses, and the compiler otherwise sinks all of it below the loads, which
+// then hold every raw byte of the run in registers.
+__device__ __forceinline__ void ds_pin(uint32_t& v) { asm volatile("" : "+v"(v)); }
+// kSteps unit rows (kN b128 loads each, step s at off_of(s)) through a ring of kDepth buffers:
+// kDepth - 1 loads ahead of the one use(s, words) reduces.  The scheduling barriers keep the
+// compiler from issuing every load first, which is what bounds the registers: at most kDepth
+// unit rows of raw bytes are live.
+template <int kN, int kSteps, int kDepth, class Off, class Use>
+__device__ __forceinline__ void ds_pipeline(__amdgpu_buffer_rsrc_t rs, Off&& off_of, Use&& use) {
+    uint32_t w[kDepth][4 * kN];
+#pragma unroll
+    for (int s = 0; s < kDepth - 1 && s < kSteps; ++s) load_words<kN>(rs, off_of(s), w[s % kDepth]);
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        if (s + kDepth - 1 < kSteps) load_words<kN>(rs, off_of(s + kDepth - 1), w[(s + kDepth - 1) % kDepth]);
+        __builtin_amdgcn_sched_barrier(0);
+        use(s, w[s % kDepth]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// The lane's run as 16 staged words.  ok: the fast path (else every load is out of range and
+// the words are discarded); off: the run's first source byte, in source rows of pitch stride;
+// NV12: coff the first Cb,Cr byte of the run's 8 cells, in chroma rows of pitch cpitch.
+// Step s = (unit s / kDs, source row s % kDs): a unit's sums are complete after its last row.
+__device__ __forceinline__ void ds_load_run(const RgbRsrc& rs, bool ok, uint32_t off, uint32_t stride, uint32_t coff,
+                                            uint32_t cpitch, uint32_t sel4, uint32_t px[16]) {
+    constexpr int kU = 16 / kDs;  // output pixels of a unit
+    constexpr int kSteps = kDs * kDs;
+    if constexpr (kShape == kShapeNv12) {
+#if JPGE_K1_SHAPE == 4
+        constexpr int kDepth = kDs == 2 ? 4 : 8;
+        uint32_t acc[kU];
+        ds_pipeline<1, kSteps, kDepth>(
+            rs.p0, [&](int s) __attribute__((always_inline)) { return ok ? off + (uint32_t)(s % kDs) * stride + 16u * (uint32_t)(s / kDs) : kOob; },
+            [&](int s, const uint32_t(&w)[4]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < kU; ++i) {
+                    acc[i] = add_bytes(w, i * kDs, 1, kDs, s % kDs ? acc[i] : 0u);
+                    ds_pin(acc[i]);
+                }
+                if (s % kDs == kDs - 1) {
+#pragma unroll
+                    for (int i = 0; i < kU; ++i) px[(s / kDs) * kU + i] = ds_mean(acc[i]);
+                }
+            });
+        // the run's 8 cells: kDs units of 8 / kDs cells, 16 bytes of Cb,Cr pairs on each of kDs chroma rows
+        constexpr int kC = 8 / kDs;
+        uint32_t cb[kC], cr[kC];
+        ds_pipeline<1, kSteps, kDepth>(
+            rs.p1, [&](int s) __attribute__((always_inline)) { return ok ? coff + (uint32_t)(s % kDs) * cpitch + 16u * (uint32_t)(s / kDs) : kOob; },
+            [&](int s, const uint32_t(&w)[4]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < kC; ++i) {
+                    cb[i] = add_bytes(w, i * kDs * 2, 2, kDs, s % kDs ? cb[i] : 0u);
+                    cr[i] = add_bytes(w, i * kDs * 2 + 1, 2, kDs, s % kDs ? cr[i] : 0u);
+                    ds_pin(cb[i]);
+                    ds_pin(cr[i]);
+                }
+                if (s % kDs == kDs - 1) {
+#pragma unroll
+                    for (int i = 0; i < kC; ++i) {
+                        const uint32_t c = (ds_mean(cb[i]) << 8) | (ds_mean(cr[i]) << 16);
+                        px[2 * ((s / kDs) * kC + i)] |= c;
+                        px[2 * ((s / kDs) * kC + i) + 1] |= c;
+                    }
+                }
+            });
+#endif
+    } else {
+        constexpr int kN = (int)kRun / 16;  // b128 loads of a unit row (3, or 4 of 4-byte pixels)
+        constexpr int kDepth = kDs == 2 ? 3 : kN == 3 ? 4 : 3;
+        uint32_t acc[kU][3];
+        ds_pipeline<kN, kSteps, kDepth>(
+            rs.p0, [&](int s) __attribute__((always_inline)) { return ok ? off + (uint32_t)(s % kDs) * stride + kRun * (uint32_t)(s / kDs) : kOob; },
+            [&](int s, const uint32_t(&w)[4 * kN]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < kU; ++i)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        acc[i][c] = add_bytes(w, i * kDs * (int)kBpp + c, (int)kBpp, kDs, s % kDs ? acc[i][c] : 0u);
+                        ds_pin(acc[i][c]);
+                    }
+                if (s % kDs == kDs - 1) {
+#pragma unroll
+                    for (int i = 0; i < kU; ++i) {
+                        const uint32_t b0 = ds_mean(acc[i][0]), b1 = ds_mean(acc[i][1]), b2 = ds_mean(acc[i][2]);
+                        uint32_t& o = px[(s / kDs) * kU + i];
+                        if constexpr (kShape == kShapeBgr8) o = b2 | (b1 << 8) | (b0 << 16);
+                        else if constexpr (kShape == kShapeX4) o = __builtin_amdgcn_perm(0u, b0 | (b1 << 8) | (b2 << 16), sel4);
+                        else o = b0 | (b1 << 8) | (b2 << 16);
+                    }
+                }
+            });
+    }
+}
+// One output pixel of the downscaling builds' clamped edge path: row oy, column ox of the
+// output frame (inside it), the mean of its kDs x kDs source pixels, their coordinates clamped
+// to the sw x sh source frame (NV12: the cell's chroma of its kDs x kDs source cells, clamped
+// to the chroma plane), by byte loads.  The sums fit 16-bit fields.
+__device__ __forceinline__ uint32_t edge_ds(const uint8_t* base, uint64_t stride, uint64_t plane_stride, uint32_t sw,
+                                            uint32_t sh, uint32_t sel4, uint32_t oy, uint32_t ox) {
+    if constexpr (kShape == kShapeNv12) {
+        const uint32_t scw = (sw + 1) / 2, sch = (sh + 1) / 2;
+        const uint8_t* cp = base + plane_stride;
+        uint32_t ys = 0, cs = 0;  // cs: Cb | Cr << 16
+#pragma unroll 1  // (rolled: the 16 pixels' loads would otherwise all be issued first, at hundreds of registers)
+        for (uint32_t r = 0; r < (uint32_t)kDs; ++r) {
+            const uint8_t* yrow = base + (uint64_t)min(kDs * oy + r, sh - 1) * stride;
+            const uint8_t* crow = cp + (uint64_t)min(kDs * (oy >> 1) + r, sch - 1) * stride;
+            for (uint32_t i = 0; i < (uint32_t)kDs; ++i) {
+                ys += yrow[min(kDs * ox + i, sw - 1)];
+                const uint8_t* c = crow + 2 * (uint64_t)min(kDs * (ox >> 1) + i, scw - 1);
+                cs += (uint32_t)c[0] | ((uint32_t)c[1] << 16);
+            }
+        }
+        return ds_mean(ys) | (ds_mean(cs & 0xFFFF) << 8) | (ds_mean(cs >> 16) << 16);
+    } else {
+        uint32_t rb = 0, gs = 0;  // rb: R | B << 16 of the staged order
+#pragma unroll 1  // (rolled, as above)
+        for (uint32_t r = 0; r < (uint32_t)kDs; ++r)
+            for (uint32_t i = 0; i < (uint32_t)kDs; ++i) {
+                const uint32_t p = edge_pixel(base, stride, plane_stride, sel4, min(kDs * oy + r, sh - 1), min(kDs * ox + i, sw - 1));
+                rb += p & 0x00FF00FFu;
+                gs += (p >> 8) & 0xFF;
+            }
+        return ds_mean(rb & 0xFFFF) | (ds_mean(gs) << 8) | (ds_mean(rb >> 16) << 16);
+    }
+}
+
 #if JPGE_K1_SHAPE >= 11
 #define JPGE_K1_OCC __attribute__((amdgpu_waves_per_eu(4, 4)))
 #else
@@ -503,6 +678,12 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     uint64_t stride_ = a.stride;
     uint32_t gw_ = a.g.width, gh_ = a.g.height;
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
+    uint32_t sw_ = gw_, sh_ = gh_;   // the frame the loads read: the downscaling builds' source
+    if constexpr (kDs > 1) {
+        sw_ = a.src_w;
+        sh_ = a.src_h;
+        asm volatile("" : "+s"(sw_), "+s"(sh_));
+    }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
     if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422)) {
@@ -537,7 +718,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     // offset (kOob) makes a load return zeros and drops a store, so every tile
     // issues the same 3 loads (4-byte pixels: 4) and 3 stores with no branch around them, and the
     // wait for the prefetched pixels leaves the previous tile's stores in flight.
-    const RgbRsrc rgb_rs = rgb_rsrc(rgb_, stride_, ps_, gw_, gh_);
+    const RgbRsrc rgb_rs = rgb_rsrc(rgb_, stride_, ps_, sw_, sh_);
     const __amdgpu_buffer_rsrc_t coef_rs =
         __builtin_amdgcn_make_buffer_rsrc(a.coef, 0, (int)(uint32_t)((uint64_t)a.g.nblocks() * 128), 0x00020000);
 
@@ -604,6 +785,24 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         load_run(rgb_rs, off, coff, v0, v1, v2, v3);
         return ok;
     };
+    // The downscaling builds: the lane's run of partition tile k, loaded and reduced to its 16
+    // staged words (ds_load_run).  The fast path's conditions are on the source: its kDs rows
+    // and 16 * kDs pixels (NV12: and the kDs chroma rows of the run's cells) lie inside the frame.
+    auto fast_load_ds = [&](uint32_t k, uint32_t nx[16]) -> bool {
+        const uint32_t t = tb_p + k;
+        const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * 4;
+        const uint32_t y = mrow * 16 + r16, xs = mcol0 * 16 + c16 * 16;
+        bool ok = k < n_p && aligned && kDs * y + kDs <= sh_ && kDs * (xs + 16) <= sw_;
+        if constexpr (kShape == kShapeNv12) ok = ok && kDs * (y >> 1) + kDs <= (sh_ + 1) / 2;
+        const uint32_t off = (uint32_t)((uint64_t)(mrow * 16 * kDs) * stride_ + (uint64_t)mcol0 * (kRun * kDs)) +
+                             (uint32_t)(r16 * kDs) * (uint32_t)stride_ + (uint32_t)c16 * (kRun * kDs);
+        uint32_t coff = 0;
+        if constexpr (kShape == kShapeNv12)
+            coff = (uint32_t)((uint64_t)(mrow * 8 * kDs) * stride_ + (uint64_t)mcol0 * (16 * kDs)) +
+                   (uint32_t)((r16 >> 1) * kDs) * (uint32_t)stride_ + (uint32_t)c16 * (16 * kDs);
+        ds_load_run(rgb_rs, ok, off, (uint32_t)stride_, coff, (uint32_t)stride_, sel4_, nx);
+        return ok;
+    };
     // The last round's 16-byte coefficient row (kOob: none) is stored during the
     // next tile, after its staging: the staging's wait for the prefetched pixels
     // then finds only long-issued stores ahead of them in the in-order counter.
@@ -612,7 +811,10 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     auto store_pending = [&] { __builtin_amdgcn_raw_buffer_store_b128(pend, coef_rs, poff, 0, kK1StoreAux); };
     uint32_t k = __builtin_amdgcn_readfirstlane((uint32_t)wv);  // this wave's current tile of the run
     uint4 c0, c1, c2, c3;
-    bool cfast = fast_load(k, c0, c1, c2, c3);  // issued before the prologue's own memory traffic
+    uint32_t nx[16];  // (the downscaling builds' prefetch: the next tile's run as staged words)
+    bool cfast;
+    if constexpr (kDs > 1) cfast = fast_load_ds(k, nx);
+    else cfast = fast_load(k, c0, c1, c2, c3);  // issued before the prologue's own memory traffic
 
     for (uint32_t i = bid * kK1Threads + tid; i < a.zero_words; i += nbk * kK1Threads) a.zero[i] = 0;
     if (bid == 0)  // carried: another frame's tables + headers, host -> device
@@ -764,7 +966,10 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         // (the prefetched registers are consumed on every path, so no later wait on
         // them can also drain the previous tile's coefficient stores)
         uint32_t px[16];
-        if constexpr (kTen) {
+        if constexpr (kDs > 1) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) px[i] = nx[i];
+        } else if constexpr (kTen) {
             unpack_yuv10(c0, c1, c2, c3, px);
         } else if constexpr (kYuv420 || kPlanes422) {
             unpack_yuv420(c0, c1, c2, (uint32_t)(c16 & 1), px);
@@ -785,7 +990,9 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         }
         if (!cfast) {  // right/bottom edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            if constexpr (kYuv)
+            if constexpr (kDs > 1)  // (of the downscaled frame, each pixel from its clamped source pixels)
+                for (int i = 0; i < 16; ++i) px[i] = edge_ds(rgb_, stride_, ps_, sw_, sh_, sel4_, sy, min(xs + i, gw_ - 1));
+            else if constexpr (kYuv)
                 for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sel4_, sy, min(xs + i, gw_ - 1));
             else
                 for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
@@ -796,8 +1003,15 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         wave_order();
         // prefetch the next tile of this wave (into the registers just staged) while
         // this one is transformed
-        store_pending();
-        cfast = fast_load(kn, c0, c1, c2, c3);
+        if constexpr (kDs > 1) {
+            // (the reduction waits for its loads: before the store, so that the wait finds only
+            // the previous tile's long-issued stores ahead of them)
+            cfast = fast_load_ds(kn, nx);
+            store_pending();
+        } else {
+            store_pending();
+            cfast = fast_load(kn, c0, c1, c2, c3);
+        }
         const uint32_t kn2 = kn < n_p ? grab() : n_p;
 
         // ---- rounds: Cb x4 + Cr x4, Y blocks 0-7 (MCUs 0, 1), Y blocks 8-15 (MCUs 2, 3) ----
@@ -888,6 +1102,12 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     uint64_t stride_ = a.stride;
     uint32_t gw_ = a.g.width, gh_ = a.g.height;
     asm volatile("" : "+s"(rgb_), "+s"(stride_), "+s"(gw_), "+s"(gh_));
+    uint32_t sw_ = gw_, sh_ = gh_;   // the frame the loads read: the downscaling builds' source
+    if constexpr (kDs > 1) {
+        sw_ = a.src_w;
+        sh_ = a.src_h;
+        asm volatile("" : "+s"(sw_), "+s"(sh_));
+    }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
     if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422)) {
@@ -922,7 +1142,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     const int r8 = lane >> 3, c8 = lane & 7;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;   // DCT: lane -> (block of the round, column)
 
-    const RgbRsrc rgb_rs = rgb_rsrc(rgb_, stride_, ps_, gw_, gh_);
+    const RgbRsrc rgb_rs = rgb_rsrc(rgb_, stride_, ps_, sw_, sh_);
     const __amdgpu_buffer_rsrc_t coef_rs =
         __builtin_amdgcn_make_buffer_rsrc(a.coef, 0, (int)(uint32_t)((uint64_t)a.g.nblocks() * 128), 0x00020000);
 
@@ -963,9 +1183,23 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     u32x4 pend;
     uint32_t poff = kOob;
     auto store_pending = [&] { __builtin_amdgcn_raw_buffer_store_b128(pend, coef_rs, poff, 0, kK1StoreAux); };
+    // (the downscaling builds, as in fdct_kernel)
+    auto fast_load_ds = [&](uint32_t k, uint32_t nx[16]) -> bool {
+        const uint32_t t = tb_p + k;
+        const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * kMcus;
+        const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
+        const bool ok = k < n_p && aligned && kDs * y + kDs <= sh_ && kDs * (xs + 16) <= sw_;
+        const uint32_t off = (uint32_t)((uint64_t)(mrow * 8 * kDs) * stride_ + (uint64_t)mcol0 * (kRun / 2 * kDs) * kYh) +
+                             (uint32_t)(r8 * kDs) * (uint32_t)stride_ + (uint32_t)c8 * (kRun * kDs);
+        ds_load_run(rgb_rs, ok, off, (uint32_t)stride_, 0u, 0u, sel4_, nx);
+        return ok;
+    };
     uint32_t k = __builtin_amdgcn_readfirstlane((uint32_t)wv);
     uint4 c0, c1, c2, c3;
-    bool cfast = fast_load(k, c0, c1, c2, c3);
+    uint32_t nx[16];
+    bool cfast;
+    if constexpr (kDs > 1) cfast = fast_load_ds(k, nx);
+    else cfast = fast_load(k, c0, c1, c2, c3);
 
     for (uint32_t i = bid * kK1Threads + tid; i < a.zero_words; i += nbk * kK1Threads) a.zero[i] = 0;
     if (bid == 0)
@@ -1005,7 +1239,10 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
 
         uint32_t px[16];
-        if constexpr (kGray) {
+        if constexpr (kDs > 1) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) px[i] = nx[i];
+        } else if constexpr (kGray) {
             unpack_gray(c0, px);
         } else if constexpr (kPlanes422) {
             unpack_yuv420(c0, c1, c2, (uint32_t)(c8 & 1), px);
@@ -1026,7 +1263,9 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         }
         if (!cfast) {  // edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            if constexpr (kYuv)
+            if constexpr (kDs > 1)
+                for (int i = 0; i < 16; ++i) px[i] = edge_ds(rgb_, stride_, ps_, sw_, sh_, sel4_, sy, min(xs + i, gw_ - 1));
+            else if constexpr (kYuv)
                 for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sel4_, sy, min(xs + i, gw_ - 1));
             else
                 for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
@@ -1035,8 +1274,13 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
 #pragma unroll
         for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
         wave_order();
-        store_pending();
-        cfast = fast_load(kn, c0, c1, c2, c3);
+        if constexpr (kDs > 1) {
+            cfast = fast_load_ds(kn, nx);
+            store_pending();
+        } else {
+            store_pending();
+            cfast = fast_load(kn, c0, c1, c2, c3);
+        }
         const uint32_t kn2 = kn < n_p ? grab() : n_p;
 
         uint32_t p[8];
@@ -1116,13 +1360,14 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
 // tiles per wave.
 constexpr uint32_t kK1WholeCuTiles = 65536;
 uint32_t k1_tiles(const Geometry& g);
-bool k1_whole_cu(const Geometry& g, bool solo);
-#if JPGE_K1_SHAPE == 0
+bool k1_whole_cu(const Geometry& g, bool solo, uint32_t ds = 1);
+#if JPGE_K1_SHAPE == 0 && JPGE_K1_DS == 1
 uint32_t k1_tiles(const Geometry& g) {
     const uint32_t per = g.row8() ? 16 / g.yh : 4;  // MCUs per tile
     return ((g.mw + per - 1) / per) * g.mh;
 }
-bool k1_whole_cu(const Geometry& g, bool solo) { return solo && k1_tiles(g) >= kK1WholeCuTiles; }
+// (a downscaled frame, ds > 1: always the 4-wave shape, whose registers hold the reduction without spilling)
+bool k1_whole_cu(const Geometry& g, bool solo, uint32_t ds) { return solo && ds <= 1 && k1_tiles(g) >= kK1WholeCuTiles; }
 #endif
 
 // (static, like the kernels: every load shape's build has its own)
@@ -1131,13 +1376,15 @@ static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, h
     const FdctArgs& a = fs.a[0];
     // (Y, Cb, Cr samples are 8-bit, maxval 255: their !kExact instances are the sample transform's)
     const bool ex = kYuv ? a.xf_on == 0 : a.maxval == 255;
-    if (k1_whole_cu(a.g, a.solo)) {
-        if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
-        else return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
-    } else {
-        if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
-        else return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+    // (the downscaling builds have the 4-wave workgroup only: k1_whole_cu is false for them)
+    if constexpr (kDs == 1) {
+        if (k1_whole_cu(a.g, a.solo)) {
+            if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+            else return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+        }
     }
+    if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+    else return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
 }
 
 template <int kFilt, int kN>
@@ -1150,10 +1397,14 @@ static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hi
         if (ex) return hipErrorInvalidValue;
         if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
-    } else if (k1_whole_cu(a.g, a.solo)) {
-        if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
-        else return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
     } else {
+        // (the downscaling builds have the 4-wave workgroup only: k1_whole_cu is false for them)
+        if constexpr (kDs == 1) {
+            if (k1_whole_cu(a.g, a.solo)) {
+                if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+                else return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+            }
+        }
         if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
         else return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     }
@@ -1193,9 +1444,9 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
     }
 }
 
-#if JPGE_K1_SHAPE != 0
+#if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1
 // this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
-// _packed422 / _nv16 / _i422 / _p010 / _i010)
+// _packed422 / _nv16 / _i422 / _p010 / _i010; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
@@ -1222,10 +1473,19 @@ hipError_t launch_fdct_p010(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid
 hipError_t launch_fdct_i010(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_p010_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_i010_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+// the downscaling builds (FdctArgs::ds 2, 4) of the shapes that have them
+hipError_t launch_fdct_rgb8_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_rgb8_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_bgr8_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_bgr8_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_x4_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_x4_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_nv12_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_nv12_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 
-uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs) {
+uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs, uint32_t ds) {
     const uint32_t tiles = k1_tiles(g);
-    if (k1_whole_cu(g, solo)) {  // one whole-CU workgroup per CU (MI355X: 256 CUs)
+    if (k1_whole_cu(g, solo, ds)) {  // one whole-CU workgroup per CU (MI355X: 256 CUs)
         const uint32_t cap = 256u * (16u / (uint32_t)kK1WavesSolo);
         return tiles < cap ? tiles : cap;
     }
@@ -1251,16 +1511,27 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
             fmt_gray(m.fmt) != m.g.gray())
             return hipErrorInvalidValue;
         static_assert(kK1OffsetBound == kOob, "the host's bound is the kernel's out-of-range offset");
-        if (!k1_offsets_fit(m.fmt, m.g, m.stride)) return hipErrorInvalidValue;
+        // a downscaled frame: g is the frame of ceil(src / ds) pixels; the offsets span the source
+        Geometry src = m.g;
+        if (m.ds > 1) {
+            if (!ds_valid((int)m.ds) || !ds_fmt(m.fmt) || !m.src_w || !m.src_h || m.g.width != ds_dim(m.src_w, (int)m.ds) ||
+                m.g.height != ds_dim(m.src_h, (int)m.ds))
+                return hipErrorInvalidValue;
+            src.width = m.src_w;
+            src.height = m.src_h;
+        }
+        if (!k1_offsets_fit(m.fmt, src, m.stride)) return hipErrorInvalidValue;
+        if ((m.ds > 1 ? m.ds : 1u) != (a.ds > 1 ? a.ds : 1u) || (m.ds > 1 && (m.src_w != a.src_w || m.src_h != a.src_h)))
+            return hipErrorInvalidValue;
         // 10-bit layouts: 16-bit words (even addresses and pitches), and always the sample transform
         if (fmt_yuv10(m.fmt) && ((((uintptr_t)m.rgb | m.stride | m.plane_stride) & 1) || !m.xf_on)) return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
             fmt_shape(m.fmt) != fmt_shape(a.fmt) || (m.xf_on != 0) != (a.xf_on != 0) ||
-            m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs))
+            m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs, m.ds))
             return hipErrorInvalidValue;
     }
     const uint32_t grid = fs.wg0[fs.n];
-    if (fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
+    if (a.ds <= 1 && fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
     if constexpr (kN == 1) {
         if (fmt_shape(a.fmt) == kShapeP010) return launch_fdct_p010_one(fs, grid, s, t);
         if (fmt_shape(a.fmt) == kShapeI010) return launch_fdct_i010_one(fs, grid, s, t);
@@ -1270,6 +1541,16 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
     w.n = fs.n;
     for (uint32_t f = 0; f < fs.n; ++f) w.a[f] = fs.a[f];
     for (uint32_t f = 0; f <= fs.n; ++f) w.wg0[f] = fs.wg0[f];
+    if (a.ds > 1) {
+        const bool d2 = a.ds == 2;
+        switch (fmt_shape(a.fmt)) {
+            case kShapeRgb8: return d2 ? launch_fdct_rgb8_d2(w, grid, s, t) : launch_fdct_rgb8_d4(w, grid, s, t);
+            case kShapeBgr8: return d2 ? launch_fdct_bgr8_d2(w, grid, s, t) : launch_fdct_bgr8_d4(w, grid, s, t);
+            case kShapeX4: return d2 ? launch_fdct_x4_d2(w, grid, s, t) : launch_fdct_x4_d4(w, grid, s, t);
+            case kShapeNv12: return d2 ? launch_fdct_nv12_d2(w, grid, s, t) : launch_fdct_nv12_d4(w, grid, s, t);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (fmt_shape(a.fmt)) {
         case kShapeBgr8: return launch_fdct_bgr8(w, grid, s, t);
         case kShapeX4: return launch_fdct_x4(w, grid, s, t);
@@ -1287,12 +1568,12 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
 }
 
 hipError_t launch_fdct(const FdctArgs& a, hipStream_t s, const KTimer* t) {
-    return launch_fdct_fs(frame_set<1>(&a, 1, fdct_grid(a.g, a.solo, a.wgs)), s, t);
+    return launch_fdct_fs(frame_set<1>(&a, 1, fdct_grid(a.g, a.solo, a.wgs, a.ds)), s, t);
 }
 
 hipError_t launch_fdct_set(const FdctArgs* a, int n, hipStream_t s, const KTimer* t) {
     if (n < 1 || n > kMaxSet) return hipErrorInvalidValue;
-    return launch_fdct_fs(frame_set(a, n, fdct_grid(a[0].g, a[0].solo, a[0].wgs)), s, t);
+    return launch_fdct_fs(frame_set(a, n, fdct_grid(a[0].g, a[0].solo, a[0].wgs, a[0].ds)), s, t);
 }
 #endif  // JPGE_K1_SHAPE == 0
 

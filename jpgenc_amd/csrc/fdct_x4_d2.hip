@@ -1,0 +1,5 @@
+// K1 for RGBA8 / BGRA8, box downscale by 2 (jpge_set_downscale): fdct.hip built with that load shape and factor (see "downscaling loads" there).
+#define JPGE_K1_SHAPE 2
+#define JPGE_K1_DS 2
+#define JPGE_K1_ENTRY launch_fdct_x4_d2
+#include "fdct.hip"

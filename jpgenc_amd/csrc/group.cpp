@@ -290,6 +290,10 @@ int jpge_group_encode_striped(jpge_group* g, const uint8_t* rgb, uint32_t width,
         int huff = JPGE_HUFF_OPTIMAL;
         if (const int st = jpge_get_huffman(c, &huff, nullptr)) return st;
         if (huff != JPGE_HUFF_OPTIMAL) return (int)JPGE_E_ARG;
+        // and codes the image at full size (the stripe phases refuse a downscale factor)
+        int factor = 1;
+        if (const int st = jpge_get_downscale(c, &factor)) return st;
+        if (factor != 1) return (int)JPGE_E_ARG;
     }
     const size_t row = (size_t)width * 3, pitch = stride ? stride : row;
     if (pitch < row) return (int)JPGE_E_ARG;

@@ -11,6 +11,7 @@
 //   ubuf  : u8 [G][kEntropyRegionBytes] each entropy workgroup's bit stream before
 //           byte alignment and 0xFF stuffing, written and re-read by that workgroup
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include <hip/hip_runtime_api.h>
@@ -152,6 +153,12 @@ struct FdctArgs {
     int maxval;      // 255 -> exact integer colour path
     bool solo;       // the kernel has the GPU to itself: whole-CU workgroups (else 4-wave ones)
     uint32_t wgs;    // pipeline grid override (0: the default cap; experiments, JPGE_FDCT_WGS)
+    // box downscale (jpge_set_downscale): 2 or 4 = g is the frame of ceil(src / ds) pixels whose
+    // samples are the rounded means of ds x ds source samples, read from a src_w x src_h frame
+    // (the downscaling load shapes, fdct.hip JPGE_K1_DS); 0 or 1: none, g is the frame at rgb.
+    // (in the padding before q, src_w and src_h in the padding before xf: no field moves, and
+    // the block keeps its size)
+    uint32_t ds = 1;
     // luma then chroma quantisers, natural order (bytes: a small kernarg block; 16-byte
     // aligned so the kernels fetch it with scalar loads, see fdct.hip q_entry)
     alignas(16) uint8_t q[128];
@@ -172,9 +179,19 @@ struct FdctArgs {
     // (in the padding after fmt; xf at the block's end: no earlier field moves)
     uint32_t xf_on = 0;
     uint64_t plane_stride = 0;
+    uint32_t src_w = 0, src_h = 0;  // ds > 1: the source frame's size (stride and plane_stride are its pitches)
     // y_off, m0..m6 (host_io.hpp YuvXf); fetched with scalar loads, like q
     alignas(16) double xf[8] = {0, 1, 0, 0, 1, 0, 0, 1};
 };
+
+static_assert(sizeof(FdctArgs) == 336 && offsetof(FdctArgs, q) == 64 && offsetof(FdctArgs, xf) == 272,
+              "the downscale fields sit in padding: the argument block's layout is unchanged");
+
+// Box downscale by 2 or 4 inside K1 (jpge.h jpge_set_downscale): the interleaved RGB layouts in
+// every subsampling mode, and NV12 (whose Cb,Cr plane is averaged in its own domain).
+JPGE_HD inline bool ds_valid(int ds) { return ds == 1 || ds == 2 || ds == 4; }
+JPGE_HD inline bool ds_fmt(int fmt) { return (fmt >= kFmtRgb8 && fmt <= kFmtBgra8) || fmt == kFmtNv12; }
+JPGE_HD inline uint32_t ds_dim(uint32_t n, int ds) { return (n + (uint32_t)ds - 1) / (uint32_t)ds; }
 
 // Stripe context of a frame (a row stripe of a larger image); the
 // defaults describe a whole frame.
@@ -436,7 +453,8 @@ inline FrameSet<A, N> frame_set(const A* a, int n, uint32_t grid_each) {
     return s;
 }
 
-uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs = 0);
+// (ds: FdctArgs::ds, a downscaled frame runs the 4-wave workgroups at every size)
+uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs = 0, uint32_t ds = 1);
 // statistics workgroups: wgs (0: 3 per CU), within the tile-table bound and the tile count
 uint32_t stats_grid(const SegLayout& L, uint32_t wgs = 0);
 // entropy partition of a frame: restart_mcus = 0 -> one segment over 128-block tiles

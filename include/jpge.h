@@ -208,6 +208,42 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * frame of s / 4: under every transform setting, Huffman mode and restart interval. */
 #define JPGE_FMT_P010 32
 #define JPGE_FMT_I010 33
+/* 10-bit 4:2:2 frames (SDI capture; ProRes, DNxHR, XAVC-Intra and HEVC RExt 4:2:2 decoders):
+ * little-endian 16-bit words, one Cb and one Cr sample per horizontal pixel pair of every row.
+ * `rgb` points at the frame's first byte and `stride` is the Y (or only) plane's pitch in BYTES.
+ * With cw = ceil(width / 2):
+ *   Y210: one plane, `height` rows of cw 8-byte groups Y0 Cb Y1 Cr; a sample is s = word >> 6,
+ *     the low six bits are never read (Y212 and Y216 data is taken at its top 10 bits); stride
+ *     0 = 8 * cw; plane_stride must be 0.  With an odd width the last group's Y1 word is storage
+ *     only: its value never reaches the output.
+ *   P210: the Y plane, then at rgb + plane_stride (0 = stride * height) a Cb,Cr plane of
+ *     `height` rows of pitch `stride`, Cb in the even words and Cr in the odd words; a sample is
+ *     s = word >> 6 (P212 and P216 likewise); stride 0 = 2 * (width rounded up to even).
+ *   I210 (yuv422p10le): a sample is s = word & 0x3FF; the high six bits are never read.  The
+ *     Cb plane at rgb + plane_stride (0 = stride * height): `height` rows of pitch
+ *     cs = 2 * ceil(stride / 4); the Cr plane at Cb + cs * height; stride 0 = 2 * width.
+ * The base, `stride` and `plane_stride` must be even, the stride not below the least for the
+ * width, and maxval 255 (else JPGE_E_ARG, or the frame's status in a batch).
+ * A frame in one of these layouts is the Y, Cb, Cr frame in which pixel (y, x) has the samples
+ * s_y[y][x], s_cb[y][x >> 1], s_cr[y][x >> 1], each entering as the exact value s / 4:
+ *   yc = 0.25 * s_y - y_off,  u = 0.25 * s_cb - 128,  v = 0.25 * s_cr - 128
+ * with the three lines of jpge_set_yuv_transform applied ALWAYS and per pixel (each product and
+ * sum rounded on its own, the clamps included; under JPGE_YUV_FULL_601 with the identity
+ * coefficients, as for P010), and after that the context's subsampling mode.  All six modes are
+ * accepted; JPGE_S422 is the native one: it keeps each cell's sample and runs no filter
+ * arithmetic.  This holds under every Huffman mode and restart interval, alone, in batches and
+ * frame sets, and through jpge_group_encode_batch.  The chroma is edge-replicated in the chroma
+ * domain: the clamped pixel's cell is the clamped cell.  Two consequences:
+ *   - a frame whose samples are all multiples of 4 gives, byte for byte, the .jpg of the 8-bit
+ *     YUYV / NV16 / I422 frame of s / 4, in every mode and setting;
+ *   - the three layouts of the same samples give the same bytes.
+ * jpge_stripe_transform and jpge_group_encode_striped refuse the three layouts, and so does an
+ * encode under jpge_set_downscale with a factor above 1 (JPGE_E_ARG, before anything is
+ * queued).  The fast path needs base, stride and plane_stride 16-byte aligned (I210: a stride
+ * that is a multiple of 32); anything else that is even works, slower. */
+#define JPGE_FMT_Y210 40
+#define JPGE_FMT_P210 41
+#define JPGE_FMT_I210 42
 /* One plane of 8-bit luminance: `height` rows of `stride` bytes (0 = width), one byte per
  * pixel; a sample v enters the transform as the value v - 128, as a Y sample above.
  * maxval must be 255 and plane_stride 0 (else JPGE_E_ARG).  The output is a baseline JPEG
@@ -233,7 +269,7 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
  * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
  * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
- * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts, the two 10-bit layouts and for
+ * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts, the two 10-bit 4:2:0 and the three 10-bit 4:2:2 layouts and for
  * JPGE_FMT_GRAY8 (stripes are three-component 4:2:0 of interleaved colour); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
 int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
 /* the current setting (plane_stride may be NULL) */

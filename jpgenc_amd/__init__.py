@@ -35,6 +35,11 @@ _FMT_420 = (JPGE_FMT_NV12, JPGE_FMT_I420)
 #: sample s enters the sample transform as s / 4, unrounded
 JPGE_FMT_P010, JPGE_FMT_I010 = 32, 33
 _FMT_420P10 = (JPGE_FMT_P010, JPGE_FMT_I010)
+#: 10-bit 4:2:2 frames of the same words (one Cb, Cr per horizontal pixel pair of every row): Y210
+#: (packed groups Y0 Cb Y1 Cr, top 10 bits), P210 (NV16's planes, top 10 bits) and I210 /
+#: yuv422p10le (I422's planes, low 10 bits); host frames from pack_yuv422p10
+JPGE_FMT_Y210, JPGE_FMT_P210, JPGE_FMT_I210 = 40, 41, 42
+_FMT_422P10 = (JPGE_FMT_Y210, JPGE_FMT_P210, JPGE_FMT_I210)
 #: 4:2:2 frames of the same samples (one Cb, Cr per horizontal pixel pair of every row): packed
 #: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 groups, NV16 (Y plane + Cb,Cr rows), I422 (three planes); host
 #: frames from pack_yuv422
@@ -663,10 +668,67 @@ def pack_yuv422(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     return f, w, h, stride
 
 
+def yuv422p10_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of a Y210, P210 or I210 frame with plane stride 0 (stride, in bytes, 0: the least one)."""
+    cw = (w + 1) // 2
+    if fmt == JPGE_FMT_Y210:
+        return (stride or 8 * cw) * h
+    if fmt == JPGE_FMT_P210:
+        return (stride or 4 * cw) * 2 * h
+    if fmt == JPGE_FMT_I210:
+        stride = stride or 2 * w
+        return stride * h + 2 * (2 * ((stride + 3) // 4)) * h
+    raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:2 one")
+
+
+def pack_yuv422p10(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
+    """(frame, w, h, stride): the (H, W) Y plane and the (H, ceil(W/2)) Cb and Cr planes of 10-bit
+    samples (uint16 values 0..1023) as one contiguous host frame of bytes in layout JPGE_FMT_Y210,
+    _P210 (each sample in its word's top 10 bits, the low six zero) or _I210 (the high six zero)
+    with the least stride and plane stride 0 (jpge.h).  The frame (a Yuv422Frame) is what encode,
+    encode_batch, fdct_quant and symbol_stats take when the input layout is `fmt`.  (Odd width:
+    the last group's second Y word, and P210's pad word per Y row, are 0.)"""
+    y, cb, cr = (np.ascontiguousarray(p) for p in (y, cb, cr))
+    for p in (y, cb, cr):
+        if p.dtype.kind not in "ui" or (p.size and (int(p.min()) < 0 or int(p.max()) > 1023)):
+            raise ValueError("pack_yuv422p10 takes integer planes of 10-bit samples (0..1023)")
+    y, cb, cr = (p.astype("<u2") for p in (y, cb, cr))
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
+    h, w = y.shape
+    cw = (w + 1) // 2
+    if cb.shape != (h, cw) or cr.shape != (h, cw):
+        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({h}, {cw}) for a {w}x{h} frame")
+    if fmt == JPGE_FMT_Y210:
+        stride = 8 * cw
+        y2 = np.zeros((h, 2 * cw), "<u2")
+        y2[:, :w] = y
+        buf = np.zeros((h, cw, 4), "<u2")
+        buf[:, :, 0], buf[:, :, 2] = y2[:, 0::2] << 6, y2[:, 1::2] << 6
+        buf[:, :, 1], buf[:, :, 3] = cb << 6, cr << 6
+        buf = buf.reshape(-1)
+    elif fmt == JPGE_FMT_P210:
+        stride = 4 * cw
+        buf = np.zeros((2 * h, 2 * cw), "<u2")  # (odd width: one pad word per Y row)
+        buf[:h, :w] = y << 6
+        buf[h:, 0::2] = cb << 6
+        buf[h:, 1::2] = cr << 6
+        buf = buf.reshape(-1)
+    elif fmt == JPGE_FMT_I210:
+        stride = 2 * w  # chroma pitch 2 * ceil(2 w / 4) = 2 * cw
+        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
+    else:
+        raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:2 one")
+    f = buf.view(np.uint8).view(Yuv422Frame)
+    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
+    return f, w, h, stride
+
+
 def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     """(width, height, row stride in bytes) of a C-contiguous frame shaped for layout `fmt`:
     (H, W, 3), (H, W, 4) or (3, H, W); GRAY8: (H, W); NV12 and I420: a pack_yuv420 frame of
-    that layout; YUYV, UYVY, NV16 and I422: a pack_yuv422 frame of that layout.  A width or
+    that layout; YUYV, UYVY, NV16 and I422: a pack_yuv422 frame of that layout; P010, I010 and
+    Y210, P210, I210: a pack_yuv420p10 / pack_yuv422p10 frame of that layout.  A width or
     height of 0 or above 65535 (a JPEG frame header's limit) is a ValueError."""
     w, h, stride = _frame_geom_any(a, fmt)
     if not (1 <= w <= 65535 and 1 <= h <= 65535):
@@ -691,6 +753,11 @@ def _frame_geom_any(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
                 a.size != yuv420p10_bytes(fmt, a.width, a.height, a.stride):
             raise ValueError(f"input layout {fmt} takes a pack_yuv420p10({fmt}, y, cb, cr) frame")
         return a.width, a.height, a.stride
+    if fmt in _FMT_422P10:
+        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
+                a.size != yuv422p10_bytes(fmt, a.width, a.height, a.stride):
+            raise ValueError(f"input layout {fmt} takes a pack_yuv422p10({fmt}, y, cb, cr) frame")
+        return a.width, a.height, a.stride
     if fmt in _FMT_422:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
                 a.size != yuv422_bytes(fmt, a.width, a.height, a.stride):
@@ -707,7 +774,7 @@ def _as_frame(a, fmt: int):
     """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
     if fmt == JPGE_FMT_GRAY8:
         a = np.ascontiguousarray(a)  # (the type is checked, not converted: a float plane is no gray frame)
-    elif fmt not in _FMT_420 and fmt not in _FMT_422 and fmt not in _FMT_420P10:
+    elif fmt not in _FMT_420 and fmt not in _FMT_422 and fmt not in _FMT_420P10 and fmt not in _FMT_422P10:
         a = np.ascontiguousarray(a, np.uint8)
     w, h, stride = _frame_geom(a, fmt)
     return np.ascontiguousarray(a, np.uint8), w, h, stride
@@ -835,7 +902,8 @@ class Encoder:
     def set_input_format(self, fmt: int, plane_stride: int = 0) -> None:
         """Input layout of the following encodes (JPGE_FMT_*): frames are then (H, W, 3),
         (H, W, 4) or, planar, (3, H, W); GRAY8: (H, W), written as a one-component JPEG;
-        NV12 and I420: pack_yuv420 frames; YUYV, UYVY, NV16 and I422: pack_yuv422 frames.  plane_stride:
+        NV12 and I420: pack_yuv420 frames; YUYV, UYVY, NV16 and I422: pack_yuv422 frames; P010 and
+        I010: pack_yuv420p10 frames; Y210, P210 and I210: pack_yuv422p10 frames.  plane_stride:
         bytes between the planes of the raw-pointer entries' planar frames (NV12, I420: from
         the Y plane to the chroma, as for NV16 and I422; 0 = stride * height; the packed 4:2:2
         layouts are one plane and take 0)."""
@@ -1139,6 +1207,96 @@ class Encoder:
             if cr.data_ptr() - c.data_ptr() != cs * ch:
                 raise ValueError(f"the Cr plane must start {cs * ch} bytes ({ch} rows) after the Cb plane")
             least = 2 * w
+        if stride < least:
+            raise ValueError("rows overlap")
+        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
+        host_out = None
+        if out is None:
+            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            out_ptr, cap = _p(host_out), host_out.size
+        else:
+            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out: a contiguous uint8 device tensor")
+            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
+        prev = self.input_format()
+        self.set_input_format(fmt, plane_stride)
+        try:
+            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
+        finally:
+            self.set_input_format(*prev)
+        return n if host_out is None else host_out[:n].tobytes()
+
+    def encode_tensor_yuv422p10(self, y_or_packed, cbcr_or_cb=None, cr=None, quality: int = 50, out=None):
+        """One 10-bit 4:2:2 frame of 2-D 16-bit torch tensors (an SDI capture buffer, or a ProRes /
+        DNxHR / HEVC RExt decoder's surface), read in place through jpge_encode_rgb8: (H, 4 * cw)
+        alone is Y210 (groups Y0 Cb Y1 Cr, samples in the words' top 10 bits; the width is
+        2 * cw, an odd width goes through encode_ptr), (H, W) + (H, 2 * cw) of interleaved Cb,Cr
+        words is P210 (top 10 bits), (H, W) + two (H, cw) is I210 (low 10 bits; cw: W halved,
+        rounded up).  The planes must be views of one allocation, on one device, at offsets the
+        layout can express (jpge.h): unit inner strides, the chroma after the Y plane, P210's
+        Cb,Cr rows at the Y pitch, I210's Cb and Cr rows at pitch 2 * ceil(Y pitch in bytes / 4)
+        with Cr H rows after Cb; else ValueError.  Every subsampling mode takes these layouts (422
+        is the native one).  Returns the .jpg bytes, or, with `out` a uint8 tensor on the frame's
+        device, writes them there and returns their length.  The encoder's input layout is the
+        same afterwards."""
+        y = y_or_packed
+        planes = [p for p in (y, cbcr_or_cb, cr) if p is not None]
+        for p in planes:
+            if p.element_size() != 2 or p.dtype.is_floating_point or p.dim() != 2 or p.device != y.device:
+                raise ValueError("encode_tensor_yuv422p10 takes 2-D 16-bit integer tensors on one device")
+        if y.numel() == 0:
+            raise ValueError(f"Y plane of shape {tuple(y.shape)}: (H, W)")
+        if cbcr_or_cb is None and cr is not None:
+            raise ValueError("a Cr plane goes with a Cb plane")
+        def pitch(p):  # a plane's row pitch in bytes (None: one row, any pitch)
+            if p.stride(1) != 1 and p.shape[1] > 1:
+                raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
+            return 2 * p.stride(0) if p.shape[0] > 1 else None
+        h = int(y.shape[0])
+        plane_stride = 0
+        if cbcr_or_cb is None:  # packed
+            if y.shape[1] % 4:
+                raise ValueError(f"packed frame of shape {tuple(y.shape)}: (H, 4 * cw), whole groups of four words")
+            cw = int(y.shape[1]) // 4
+            w = 2 * cw
+            fmt = JPGE_FMT_Y210
+            stride = pitch(y)
+            stride = stride if stride is not None else 8 * cw
+            least = 8 * cw
+        else:
+            w = int(y.shape[1])
+            cw = (w + 1) // 2
+            c = cbcr_or_cb
+            if cr is None and tuple(c.shape) == (h, 2 * cw):
+                fmt = JPGE_FMT_P210
+            elif cr is not None and tuple(c.shape) == (h, cw) == tuple(cr.shape):
+                fmt = JPGE_FMT_I210
+            else:
+                raise ValueError(f"chroma of shapes {[tuple(p.shape) for p in planes[1:]]} for a {w}x{h} Y plane: "
+                                 f"({h}, {2 * cw}) or two ({h}, {cw})")
+            store = y.untyped_storage().data_ptr()
+            if any(p.untyped_storage().data_ptr() != store for p in planes):
+                raise ValueError("the planes must be views of one allocation")
+            stride = pitch(y)
+            plane_stride = c.data_ptr() - y.data_ptr()
+            if plane_stride <= 0:
+                raise ValueError("the chroma must follow the Y plane in memory")
+            if fmt == JPGE_FMT_P210:
+                cp = pitch(c)
+                stride = stride if stride is not None else 4 * cw
+                if cp is not None and cp != stride:
+                    raise ValueError(f"chroma pitch {cp}: P210's Cb,Cr rows have the Y pitch {stride}")
+                least = 4 * cw
+            else:
+                cp, rp = pitch(c), pitch(cr)
+                if stride is None:
+                    stride = 2 * w
+                cs = 2 * ((stride + 3) // 4)
+                if any(q is not None and q != cs for q in (cp, rp)):
+                    raise ValueError(f"chroma pitches {cp}, {rp}: I210's are 2 * ceil(Y pitch / 4) = {cs}")
+                if cr.data_ptr() - c.data_ptr() != cs * h:
+                    raise ValueError(f"the Cr plane must start {cs * h} bytes ({h} rows) after the Cb plane")
+                least = 2 * w
         if stride < least:
             raise ValueError("rows overlap")
         flags = JPGE_DEVICE_INPUT if y.is_cuda else 0

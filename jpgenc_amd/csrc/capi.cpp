@@ -180,7 +180,7 @@ const char* jpge_strerror(int s) {
     }
 }
 
-int jpge_version(void) { return 104; }
+int jpge_version(void) { return 105; }
 
 int jpge_device_count(int* n) {
     if (!n) return JPGE_E_ARG;

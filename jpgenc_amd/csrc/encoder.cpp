@@ -734,12 +734,13 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     // the device copy of a host frame: the same layout at pitch dev_pitch, plane stride
     // dev_pitch * height (I420: a 16-byte aligned chroma pitch, half of it)
     // (the packed 4:2:2 layouts are one plane of rows, NV16 two equal planes: the generic
-    // copies; I422 has I420's chroma planes with a row per pixel row)
-    const bool half = fmt_yuv420(f.fmt) || f.fmt == kFmtI422;
-    const size_t dev_pitch = align_up(row, f.fmt == kFmtI420 || f.fmt == kFmtI422 || f.fmt == kFmtI010 ? 32 : 16);
+    // copies; I422 has I420's chroma planes with a row per pixel row; Y210, P210 and I210 are
+    // to P010 and I010 what the packed layouts, NV16 and I422 are to NV12 and I420)
+    const bool half = fmt_yuv420(f.fmt) || f.fmt == kFmtI422 || f.fmt == kFmtI210;
+    const size_t dev_pitch = align_up(row, f.fmt == kFmtI420 || f.fmt == kFmtI422 || f.fmt == kFmtI010 || f.fmt == kFmtI210 ? 32 : 16);
     const size_t dev_plane = dev_pitch * f.height;
-    const size_t crows = f.fmt == kFmtI422 ? f.height : chroma_dim(f.height),
-                 crow = f.fmt == kFmtNv12 || f.fmt == kFmtP010 ? row : (size_t)fmt_bpp(f.fmt) * chroma_dim(f.width);  // (4:2:0 layouts, I422)
+    const size_t crows = f.fmt == kFmtI422 || f.fmt == kFmtI210 ? f.height : chroma_dim(f.height),
+                 crow = f.fmt == kFmtNv12 || f.fmt == kFmtP010 ? row : (size_t)fmt_bpp(f.fmt) * chroma_dim(f.width);  // (4:2:0 layouts, I422, I210)
     const size_t cpitch = (size_t)fmt_chroma_pitch(f.fmt, stride), dev_cpitch = (size_t)fmt_chroma_pitch(f.fmt, dev_pitch);
     const size_t dev_bytes = half ? dev_plane + (planes - 1) * dev_cpitch * crows : planes * dev_plane;
     const bool dev_in = (flags & kFlagDeviceInput) != 0, dev_out = (flags & kFlagDeviceOutput) != 0;

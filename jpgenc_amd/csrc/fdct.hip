@@ -172,7 +172,7 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
 #define JPGE_K1_SHAPE 0
 #endif
 constexpr int kShape = JPGE_K1_SHAPE;
-static_assert(kShape >= kShapeRgb8 && kShape <= kShapeI010, "JPGE_K1_SHAPE");
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapeI210, "JPGE_K1_SHAPE");
 // The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
 // layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
 // conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
@@ -187,8 +187,13 @@ constexpr bool kGray = kShape == kShapeGray;
 // each the exact fp64 value s / 4 in 8-bit units, and have the !kExact instances only: the
 // sample transform always runs (FULL_601: with the identity), because its clamps are what
 // keeps 1023 / 4 = 255.75 inside an 8-bit sample's interval.
-constexpr bool kTen = kShape == kShapeP010 || kShape == kShapeI010;
-constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420 || kTen;
+// The 10-bit 4:2:2 shapes (Y210, P210, I210) stage the same ten-bit words, a cell's chroma pair in
+// both of its pixels (cell x >> 1 of the pixel's own row), and have the !kExact instance of every
+// kernel the planar 4:4:4 shape has: each mode's filter runs on the chroma-repeated frame.
+constexpr bool kTen422 = kShape == kShapeY210 || kShape == kShapeP210 || kShape == kShapeI210;
+constexpr bool kTen = kShape == kShapeP010 || kShape == kShapeI010 || kTen422;
+constexpr bool kTenHi = kShape == kShapeP010 || kShape == kShapeP210;  // planes of words that hold a sample in their top 10 bits
+constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420 || (kTen && !kTen422);
 // The 4:2:2 shapes (YUYV / UYVY, NV16, I422) stage the same words, a cell's chroma sample in
 // both of its pixels (cell x >> 1 of the pixel's own row), and have every instance the planar
 // 4:4:4 shape has: each mode's filter then runs on the chroma-repeated frame.  In 4:2:2 the
@@ -197,7 +202,7 @@ constexpr bool kPacked422 = kShape == kShapePacked422;
 constexpr bool kPlanes422 = kShape == kShapeNv16 || kShape == kShapeI422;  // chroma loads of their own, row = pixel row
 constexpr bool kPairs = kShape == kShapeNv12 || kShape == kShapeNv16;      // Cb,Cr byte pairs
 constexpr bool kHalfPitch = kShape == kShapeI420 || kShape == kShapeI422;  // chroma pitch (stride + 1) / 2
-constexpr uint32_t kBpp = kShape == kShapeX4 ? 4u : kPacked422 || kTen ? 2u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
+constexpr uint32_t kBpp = kShape == kShapeX4 || kShape == kShapeY210 ? 4u : kPacked422 || kTen ? 2u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
 constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
 // The downscaling builds (JPGE_K1_DS 2 or 4; FdctArgs::ds) of the RGB8, BGR8, 4-byte and NV12
 // shapes: a staged word holds the rounded means of kDs x kDs source samples, so the lane's run
@@ -272,16 +277,29 @@ __device__ __forceinline__ void unpack_yuv420(const uint4& v0, const uint4& v1, 
 }
 // The 10-bit layouts' run: v0, v1 the 16 Y words, two per register.  P010 (a sample is its
 // word's top 10 bits): v2, v3 the 8 Cb,Cr word pairs of the run's cells, one per register.
-// I010 (the low 10 bits): v2 the cells' 8 Cb words, v3 their 8 Cr words.
+// I010 (the low 10 bits): v2 the cells' 8 Cb words, v3 their 8 Cr words.  (P210 and I210: the
+// same words, of the pixels' own chroma row.)  Y210 (the top 10 bits): v0..v3 the run's 8 groups
+// Y0 Cb Y1 Cr, a group per register pair, Y0 | Cb << 16 and Y1 | Cr << 16.
 __device__ __forceinline__ void unpack_yuv10(const uint4& v0, const uint4& v1, const uint4& v2, const uint4& v3,
                                              uint32_t px[16]) {
+    if constexpr (kShape == kShapeY210) {
+        const uint32_t g[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+#pragma unroll
+        for (int cell = 0; cell < 8; ++cell) {
+            const uint32_t a = g[2 * cell], b = g[2 * cell + 1];
+            const uint32_t cc = ((a >> 12) & 0x000FFC00u) | ((b >> 2) & 0x3FF00000u);  // s_cb << 10 | s_cr << 20
+            px[2 * cell] = __builtin_amdgcn_ubfe(a, 6u, 10u) | cc;
+            px[2 * cell + 1] = __builtin_amdgcn_ubfe(b, 6u, 10u) | cc;
+        }
+        return;
+    }
     const uint32_t y[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
     const uint32_t c[8] = {v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
-    constexpr uint32_t lo = kShape == kShapeP010 ? 6u : 0u;  // the sample's first bit in its word
+    constexpr uint32_t lo = kTenHi ? 6u : 0u;  // the sample's first bit in its word
 #pragma unroll
     for (int cell = 0; cell < 8; ++cell) {
         uint32_t cc;  // s_cb << 10 | s_cr << 20
-        if constexpr (kShape == kShapeP010) {
+        if constexpr (kTenHi) {
             cc = ((c[cell] << 4) & 0x000FFC00u) | ((c[cell] >> 2) & 0x3FF00000u);
         } else {
             const uint32_t sh = 16u * (uint32_t)(cell & 1);
@@ -352,8 +370,21 @@ __device__ __forceinline__ uint32_t edge_yuv(const uint8_t* base, uint64_t strid
         // 16-bit little-endian words, by byte loads: P010 the word's top 10 bits, Cb,Cr word
         // pairs in rows of pitch stride; I010 the low 10 bits, planes of pitch 2 * ceil(stride / 4)
         auto word = [](const uint8_t* q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8); };
+        // (the 4:2:2 ones: the pixel's own chroma row; Y210: the pixel's group of four words)
+        if constexpr (kShape == kShapeY210) {
+            const uint8_t* p = base + (uint64_t)sy * stride + 8 * (uint64_t)(sx >> 1);
+            return (word(p + 4 * (sx & 1)) >> 6) | ((word(p + 2) >> 6) << 10) | ((word(p + 6) >> 6) << 20);
+        }
         const uint8_t* c = base + plane_stride;
-        if constexpr (kShape == kShapeP010) {
+        if constexpr (kShape == kShapeP210) {
+            c += (uint64_t)sy * stride + 4 * (uint64_t)(sx >> 1);
+            return (word(base + (uint64_t)sy * stride + 2 * (uint64_t)sx) >> 6) | ((word(c) >> 6) << 10) | ((word(c + 2) >> 6) << 20);
+        } else if constexpr (kShape == kShapeI210) {
+            const uint64_t cs = 2 * ((stride + 3) / 4);
+            c += (uint64_t)sy * cs + 2 * (uint64_t)(sx >> 1);
+            return (word(base + (uint64_t)sy * stride + 2 * (uint64_t)sx) & 0x3FF) | ((word(c) & 0x3FF) << 10) |
+                   ((word(c + cs * gh) & 0x3FF) << 20);
+        } else if constexpr (kShape == kShapeP010) {
             c += (uint64_t)(sy >> 1) * stride + 4 * (uint64_t)(sx >> 1);
             return (word(base + (uint64_t)sy * stride + 2 * (uint64_t)sx) >> 6) | ((word(c) >> 6) << 10) | ((word(c + 2) >> 6) << 20);
         } else {
@@ -406,15 +437,15 @@ __device__ __forceinline__ uint32_t edge_pixel(const uint8_t* rgb, uint64_t stri
 // inside their row, so the range is the last row's end.
 struct RgbRsrc {
     __amdgpu_buffer_rsrc_t p0;
-#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7 && JPGE_K1_SHAPE != 8
+#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7 && JPGE_K1_SHAPE != 8 && JPGE_K1_SHAPE != 13
     __amdgpu_buffer_rsrc_t p1, p2;  // (NV12, NV16: p2 repeats p1, unused)
 #endif
 };
 __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride, uint64_t plane_stride, uint32_t gw,
                                             uint32_t gh) {
-    // (packed 4:2:2: a row is ceil(gw / 2) whole groups)
+    // (packed 4:2:2: a row is ceil(gw / 2) whole groups, of 4 bytes or, Y210, 8)
     const int range =
-        (int)(uint32_t)((uint64_t)stride * (gh - 1) + (kPacked422 ? 4 * (uint64_t)((gw + 1) / 2) : (uint64_t)kBpp * gw));
+        (int)(uint32_t)((uint64_t)stride * (gh - 1) + (kPacked422 || kShape == kShapeY210 ? kBpp * 2 * (uint64_t)((gw + 1) / 2) : (uint64_t)kBpp * gw));
     uint8_t* b = const_cast<uint8_t*>(rgb);
     RgbRsrc r;
     r.p0 = __builtin_amdgcn_make_buffer_rsrc(b, 0, range, 0x00020000);
@@ -453,6 +484,19 @@ __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride,
     const int crange = (int)(uint32_t)(cs * (ch - 1) + 2 * (uint64_t)cw);
     r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, crange, 0x00020000);
     r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride + cs * ch, 0, crange, 0x00020000);
+#elif JPGE_K1_SHAPE == 14
+    // the Cb,Cr plane: gh rows of pitch stride, cw pairs of 16-bit words each
+    const uint32_t cw = (gw + 1) / 2;
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, (int)(uint32_t)(stride * (gh - 1) + 4 * (uint64_t)cw),
+                                             0x00020000);
+    r.p2 = r.p1;
+#elif JPGE_K1_SHAPE == 15
+    // the Cb plane, then the Cr plane: gh rows of pitch cs, cw 16-bit words each
+    const uint32_t cw = (gw + 1) / 2;
+    const uint64_t cs = 2 * ((stride + 3) / 4);
+    const int crange = (int)(uint32_t)(cs * (gh - 1) + 2 * (uint64_t)cw);
+    r.p1 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride, 0, crange, 0x00020000);
+    r.p2 = __builtin_amdgcn_make_buffer_rsrc(b + plane_stride + cs * gh, 0, crange, 0x00020000);
 #elif JPGE_K1_SHAPE == 10
     // the Cb plane, then the Cr plane: gh rows of pitch cs, cw bytes each
     const uint32_t cw = (gw + 1) / 2;
@@ -482,12 +526,18 @@ __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, coff, 0, 0));
 #elif JPGE_K1_SHAPE == 7
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
-#elif JPGE_K1_SHAPE == 11 || JPGE_K1_SHAPE == 12
-    // 32 bytes of Y; P010: the 32 bytes of Cb,Cr pairs under them; I010: 16 bytes of each plane
+#elif JPGE_K1_SHAPE == 13
+    // the run's 8 groups
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
+    v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 32, 0, 0));
+    v3 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 48, 0, 0));
+#elif JPGE_K1_SHAPE == 11 || JPGE_K1_SHAPE == 12 || JPGE_K1_SHAPE == 14 || JPGE_K1_SHAPE == 15
+    // 32 bytes of Y; P010, P210: the 32 bytes of Cb,Cr pairs under them; I010, I210: 16 bytes of each plane
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff, 0, 0));
-    v3 = kShape == kShapeP010 ? as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff + 16, 0, 0))
+    v3 = kTenHi ? as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p1, coff + 16, 0, 0))
                               : as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p2, coff, 0, 0));
 #else
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
@@ -686,7 +736,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422)) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -709,8 +759,8 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     const uint32_t tiles_per_row = (mw + 3) / 4;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    // (I420, I422: the chroma pitch, half the stride, is 16-byte aligned too)
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010) || (stride_ & 31) == 0);
+    // (I420, I422, I010, I210: the chroma pitch, half the stride, is 16-byte aligned too)
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010 || kShape == kShapeI210) || (stride_ & 31) == 0);
     const int r16 = lane >> 2, c16 = lane & 3;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;     // DCT: lane -> (block of the round, column)
 
@@ -748,10 +798,12 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         lane_coff = (uint32_t)(r16 >> 1) * cpitch + (kShape == kShapeNv12 ? (uint32_t)c16 : (uint32_t)(c16 >> 1)) * 16;
     }
     // 10-bit: P010 the 32 bytes of pairs under the run, I010 the 16 bytes of each plane that are its 8 cells
-    constexpr uint32_t kCellRun = kShape == kShapeP010 ? 32u : 16u;  // chroma bytes (of one plane) of 8 cells
+    // (P210, I210: the same bytes of chroma row (tile row * 16 + r16), the pixels' own; Y210: no chroma loads)
+    constexpr uint32_t kCellRun = kTenHi ? 32u : 16u;  // chroma bytes (of one plane) of 8 cells
+    constexpr uint32_t kCRows = kTen422 ? 16u : 8u;    // chroma rows of a tile
     if constexpr (kTen) {
-        cpitch = kShape == kShapeP010 ? (uint32_t)stride_ : (uint32_t)(2 * ((stride_ + 3) / 4));
-        lane_coff = (uint32_t)(r16 >> 1) * cpitch + (uint32_t)c16 * kCellRun;
+        cpitch = kTenHi ? (uint32_t)stride_ : (uint32_t)(2 * ((stride_ + 3) / 4));
+        lane_coff = (uint32_t)(kTen422 ? r16 : r16 >> 1) * cpitch + (uint32_t)c16 * kCellRun;
     }
     // NV16, I422: the same bytes of chroma row (tile row * 16 + r16), the pixels' own
     if constexpr (kPlanes422) {
@@ -775,7 +827,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         }
         if constexpr (kTen) {
             // (I010: the run's 8 cells are the 16 bytes themselves, inside their row whenever the run is)
-            const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * kCellRun);
+            const uint32_t cbase = (uint32_t)((uint64_t)(mrow * kCRows) * cpitch + (uint64_t)mcol0 * kCellRun);
             coff = ok ? cbase + lane_coff : kOob;
         }
         if constexpr (kPlanes422) {
@@ -862,7 +914,8 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     auto y_inputs = [&](const uint32_t p[8], double x[8]) {
         if constexpr (kYuv && !kExact) {
             // the sample transform; a 4:2:0 layout's rows 2r, 2r + 1 lie in one cell (yrow0 is
-            // even), so the chroma bytes are converted and scaled once per pair
+            // even), so the chroma bytes are converted and scaled once per pair (the 4:2:2
+            // layouts, 8-bit and 10-bit: per pixel, the two rows hold different chroma)
             constexpr int n = kYuv420 ? 2 : 1;
 #pragma unroll
             for (int i = 0; i < 8; i += n) {
@@ -1091,7 +1144,7 @@ constexpr int kRgbPitch444 = 130;  // u32 per staged row of 128 px (+2: even, fo
 static_assert(8 * kRgbPitch444 <= 16 * kRgbPitch, "the 4:4:4 tile fits the 4:2:0 staging area");
 
 template <bool kExact, int kWaves, int kYh, int kN>
-__global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArgs, kN> fs) {
+__global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(FrameSet<FdctArgs, kN> fs) {
     const uint32_t set_f = set_member<kN>(fs.wg0, fs.n, blockIdx.x);  // (frame sets: kernels.hpp)
     const FdctArgs& a = fs.a[set_f];
     const uint32_t bid = blockIdx.x - fs.wg0[set_f], nbk = fs.wg0[set_f + 1] - fs.wg0[set_f];
@@ -1110,7 +1163,7 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422)) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -1137,8 +1190,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
     const uint32_t tiles_per_row = (mw + kMcus - 1) / kMcus;
     const uint32_t ntiles = tiles_per_row * a.g.mh;
     const double scale = 255.0 / (double)a.maxval;  // Image.cpp:465
-    // (I420, I422: the chroma pitch, half the stride, is 16-byte aligned too)
-    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010) || (stride_ & 31) == 0);
+    // (I420, I422, I010, I210: the chroma pitch, half the stride, is 16-byte aligned too)
+    const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010 || kShape == kShapeI210) || (stride_ & 31) == 0);
     const int r8 = lane >> 3, c8 = lane & 7;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;   // DCT: lane -> (block of the round, column)
 
@@ -1162,6 +1215,12 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         cpitch = kPairs ? (uint32_t)stride_ : (uint32_t)((stride_ + 1) / 2);
         lane_coff = (uint32_t)r8 * cpitch + (kPairs ? (uint32_t)c8 : (uint32_t)(c8 >> 1)) * 16;
     }
+    // P210, I210: the 32 bytes of pairs under the run, or the 16 bytes of each plane that are its 8 cells
+    constexpr uint32_t kCellRun = kTenHi ? 32u : 16u;  // chroma bytes (of one plane) of 8 cells
+    if constexpr (kTen) {
+        cpitch = kTenHi ? (uint32_t)stride_ : (uint32_t)(2 * ((stride_ + 3) / 4));
+        lane_coff = (uint32_t)r8 * cpitch + (uint32_t)c8 * kCellRun;
+    }
     auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * kMcus;
@@ -1175,6 +1234,11 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
         if constexpr (kPlanes422) {
             // the tile's 128 px: 128 bytes of Cb,Cr pairs (NV16), or 64 of each plane (I422)
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kPairs ? 8 : 4) * kYh);
+            coff = ok ? cbase + lane_coff : kOob;
+        }
+        if constexpr (kTen) {
+            // (I210: the run's 8 cells are the 16 bytes themselves, inside their row whenever the run is)
+            const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kCellRun / 2) * kYh);
             coff = ok ? cbase + lane_coff : kOob;
         }
         load_run(rgb_rs, off, coff, v0, v1, v2, v3);
@@ -1244,6 +1308,8 @@ __global__ __launch_bounds__(kWaves * 64) void fdct_row8_kernel(FrameSet<FdctArg
             for (int i = 0; i < 16; ++i) px[i] = nx[i];
         } else if constexpr (kGray) {
             unpack_gray(c0, px);
+        } else if constexpr (kTen) {
+            unpack_yuv10(c0, c1, c2, c3, px);
         } else if constexpr (kPlanes422) {
             unpack_yuv420(c0, c1, c2, (uint32_t)(c8 & 1), px);
         } else if constexpr (kPacked422) {
@@ -1376,15 +1442,22 @@ static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, h
     const FdctArgs& a = fs.a[0];
     // (Y, Cb, Cr samples are 8-bit, maxval 255: their !kExact instances are the sample transform's)
     const bool ex = kYuv ? a.xf_on == 0 : a.maxval == 255;
-    // (the downscaling builds have the 4-wave workgroup only: k1_whole_cu is false for them)
-    if constexpr (kDs == 1) {
-        if (k1_whole_cu(a.g, a.solo)) {
-            if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
-            else return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+    if constexpr (kTen) {
+        // 10-bit samples always go through the sample transform: no kExact instance
+        if (ex) return hipErrorInvalidValue;
+        if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+        return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+    } else {
+        // (the downscaling builds have the 4-wave workgroup only: k1_whole_cu is false for them)
+        if constexpr (kDs == 1) {
+            if (k1_whole_cu(a.g, a.solo)) {
+                if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+                else return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
+            }
         }
+        if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+        else return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     }
-    if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
-    else return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
 }
 
 template <int kFilt, int kN>
@@ -1446,12 +1519,12 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
 
 #if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1
 // this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
-// _packed422 / _nv16 / _i422 / _p010 / _i010; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...)
+// _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
 #if JPGE_K1_SHAPE >= 11
-// the 10-bit shapes also have the lone frame's instance (launch_fdct_p010_one / _i010_one), as the RGB8 shape has
+// the 10-bit shapes also have the lone frame's instance (launch_fdct_p010_one / _i010_one / _y210_one / ...), as the RGB8 shape has
 #define JPGE_K1_CAT_(a, b) a##b
 #define JPGE_K1_CAT(a, b) JPGE_K1_CAT_(a, b)
 hipError_t JPGE_K1_CAT(JPGE_K1_ENTRY, _one)(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
@@ -1473,6 +1546,12 @@ hipError_t launch_fdct_p010(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid
 hipError_t launch_fdct_i010(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_p010_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_i010_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_y210(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_p210(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_i210(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_y210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_p210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_i210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 // the downscaling builds (FdctArgs::ds 2, 4) of the shapes that have them
 hipError_t launch_fdct_rgb8_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_rgb8_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
@@ -1535,6 +1614,9 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
     if constexpr (kN == 1) {
         if (fmt_shape(a.fmt) == kShapeP010) return launch_fdct_p010_one(fs, grid, s, t);
         if (fmt_shape(a.fmt) == kShapeI010) return launch_fdct_i010_one(fs, grid, s, t);
+        if (fmt_shape(a.fmt) == kShapeY210) return launch_fdct_y210_one(fs, grid, s, t);
+        if (fmt_shape(a.fmt) == kShapeP210) return launch_fdct_p210_one(fs, grid, s, t);
+        if (fmt_shape(a.fmt) == kShapeI210) return launch_fdct_i210_one(fs, grid, s, t);
     }
     // the other load shapes have the frame-set instance only (a lone frame is a set of one)
     FrameSet<FdctArgs, kMaxSet> w{};
@@ -1563,6 +1645,9 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         case kShapeI422: return launch_fdct_i422(w, grid, s, t);
         case kShapeP010: return launch_fdct_p010(w, grid, s, t);
         case kShapeI010: return launch_fdct_i010(w, grid, s, t);
+        case kShapeY210: return launch_fdct_y210(w, grid, s, t);
+        case kShapeP210: return launch_fdct_p210(w, grid, s, t);
+        case kShapeI210: return launch_fdct_i210(w, grid, s, t);
         default: return launch_fdct_planar(w, grid, s, t);
     }
 }

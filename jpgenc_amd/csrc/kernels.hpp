@@ -69,19 +69,26 @@ constexpr int kFmtYuyv = 20, kFmtUyvy = 21, kFmtNv16 = 22, kFmtI422 = 23;
 // bits of its word) and I010 (I420's planes, a sample in the low 10 bits).  A sample s is the
 // exact fp64 value s / 4 in 8-bit units, and always goes through the sample transform.
 constexpr int kFmtP010 = 32, kFmtI010 = 33;
+// 10-bit 4:2:2 frames of the same words, one Cb and one Cr per horizontal pixel pair of every row:
+// Y210 (packed groups Y0 Cb Y1 Cr of four words, a sample in its word's top 10 bits), P210 (NV16's
+// planes, top 10 bits), I210 (I422's planes, low 10 bits).  A frame is the frame of samples
+// s_y[y][x], s_cb[y][x >> 1], s_cr[y][x >> 1], each s / 4, in every subsampling mode.
+constexpr int kFmtY210 = 40, kFmtP210 = 41, kFmtI210 = 42;
 // one plane of 8-bit luminance samples (a sample v is the fp64 value v - 128, as a Y sample
 // above): a one-component stream, Geometry::gray(), whatever the subsampling mode
 constexpr int kFmtGray8 = 8;
 JPGE_HD inline bool fmt_valid(int fmt) {
     return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar) ||
-           (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt == kFmtP010 || fmt == kFmtI010;
+           (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt == kFmtP010 || fmt == kFmtI010 ||
+           (fmt >= kFmtY210 && fmt <= kFmtI210);
 }
 JPGE_HD inline bool fmt_gray(int fmt) { return fmt == kFmtGray8; }
 JPGE_HD inline bool fmt_yuv(int fmt) { return fmt >= kFmtNv12; }
-JPGE_HD inline bool fmt_yuv10(int fmt) { return fmt == kFmtP010 || fmt == kFmtI010; }  // 16-bit words of 10-bit samples
-JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420 || fmt_yuv10(fmt); }  // chroma planes at half size
-JPGE_HD inline bool fmt_yuv422(int fmt) { return fmt >= kFmtYuyv && fmt <= kFmtI422; }  // chroma at half width, every row
-JPGE_HD inline bool fmt_packed422(int fmt) { return fmt == kFmtYuyv || fmt == kFmtUyvy; }
+JPGE_HD inline bool fmt_yuv422p10(int fmt) { return fmt >= kFmtY210 && fmt <= kFmtI210; }  // 10-bit, chroma at half width, every row
+JPGE_HD inline bool fmt_yuv10(int fmt) { return fmt == kFmtP010 || fmt == kFmtI010 || fmt_yuv422p10(fmt); }  // 16-bit words of 10-bit samples
+JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420 || fmt == kFmtP010 || fmt == kFmtI010; }  // chroma planes at half size
+JPGE_HD inline bool fmt_yuv422(int fmt) { return (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt_yuv422p10(fmt); }  // chroma at half width, every row
+JPGE_HD inline bool fmt_packed422(int fmt) { return fmt == kFmtYuyv || fmt == kFmtUyvy; }  // (8-bit: 4-byte groups)
 constexpr int kShapeRgb8 = 0;    // 48 bytes R,G,B,...: three b128 loads
 constexpr int kShapeBgr8 = 1;    // the same loads, bytes 2,1,0 of each pixel
 constexpr int kShapeX4 = 2;      // RGBA8 / BGRA8: 64 bytes, four b128 loads, a wave-uniform byte selector
@@ -95,28 +102,33 @@ constexpr int kShapeNv16 = 9;    // the NV12 shape's two loads, the Cb,Cr row th
 constexpr int kShapeI422 = 10;   // the I420 shape's three loads, the chroma rows those of the pixels
 constexpr int kShapeP010 = 11;   // 32 Y bytes (16 words) + the 32 bytes of Cb,Cr word pairs under them: four b128 loads
 constexpr int kShapeI010 = 12;   // 32 Y bytes + the 16 Cb bytes + the 16 Cr bytes of the run's 8 cells: four b128 loads
+constexpr int kShapeY210 = 13;   // the run's 64 bytes (8 groups of four words): four b128 loads
+constexpr int kShapeP210 = 14;   // the P010 shape's four loads, the Cb,Cr row that of the pixels
+constexpr int kShapeI210 = 15;   // the I010 shape's four loads, the chroma rows those of the pixels
 JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
+    return fmt == kFmtY210 ? kShapeY210 : fmt == kFmtP210 ? kShapeP210 : fmt == kFmtI210 ? kShapeI210 : fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
          : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
 }
 // bytes per pixel within a row (planar: of one plane), and planes
 JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt_packed422(fmt) || fmt_yuv10(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
-JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 || fmt == kFmtP010 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
+JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) || fmt == kFmtY210 ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 || fmt == kFmtP010 || fmt == kFmtP210 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
 // The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
 // that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs; NV16 likewise; the packed
-// 4:2:2 layouts: ceil(width / 2) whole 4-byte groups).
+// 4:2:2 layouts: ceil(width / 2) whole 4-byte groups; Y210: whole 8-byte groups).
 JPGE_HD inline uint64_t fmt_row_bytes(int fmt, uint32_t width) {
     if (fmt_packed422(fmt)) return 4 * (((uint64_t)width + 1) / 2);
-    if (fmt == kFmtP010) return 2 * (((uint64_t)width + 1) & ~(uint64_t)1);  // (16-bit words; I010: 2 * width, by fmt_bpp)
+    if (fmt == kFmtY210) return 8 * (((uint64_t)width + 1) / 2);
+    if (fmt == kFmtP010 || fmt == kFmtP210) return 2 * (((uint64_t)width + 1) & ~(uint64_t)1);  // (16-bit words; I010, I210: 2 * width, by fmt_bpp)
     return fmt == kFmtNv12 || fmt == kFmtNv16 ? ((uint64_t)width + 1) & ~(uint64_t)1 : (uint64_t)fmt_bpp(fmt) * width;
 }
 // The 4:2:0 layouts' chroma: ceil(height / 2) rows of ceil(width / 2) samples, starting
 // plane_stride bytes after the Y plane; row pitch `stride` (NV12, 2 bytes per sample) or
 // (stride + 1) / 2 (I420, whose Cr plane follows the Cb plane's rows).  NV16 and I422: the
 // same pitches and order, `height` rows of ceil(width / 2) samples.
-// I010: 2 * ceil(stride / 4), whole 16-bit words; P010: stride.
+// I010: 2 * ceil(stride / 4), whole 16-bit words; P010: stride.  P210 and I210: the same pitches
+// and order, `height` rows.
 JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) {
-    return fmt == kFmtI010 ? 2 * ((stride + 3) / 4) : fmt == kFmtI420 || fmt == kFmtI422 ? (stride + 1) / 2 : stride;
+    return fmt == kFmtI010 || fmt == kFmtI210 ? 2 * ((stride + 3) / 4) : fmt == kFmtI420 || fmt == kFmtI422 ? (stride + 1) / 2 : stride;
 }
 JPGE_HD inline uint32_t chroma_dim(uint32_t n) { return (n + 1) / 2; }
 // The transform kernel reaches a frame's pixels and its coefficients through 32-bit buffer
@@ -172,7 +184,7 @@ struct FdctArgs {
     uint32_t imp_n16;
     uint64_t* dbg;   // diagnostic phase stamps (JPGE_STAMPS builds), else unused
     // input layout (kFmt*); planar: plane c's rows start at rgb + c * plane_stride
-    // (NV12, I420, NV16, I422: the chroma starts at rgb + plane_stride, see fmt_chroma_pitch)
+    // (NV12, I420, NV16, I422 and the 10-bit planar layouts: the chroma starts at rgb + plane_stride, see fmt_chroma_pitch)
     int fmt = kFmtRgb8;
     // 1: the Y, Cb, Cr and gray shapes convert each sample by xf (jpge_set_yuv_transform, a
     // preset other than FULL_601): their !kExact instances.  The other shapes ignore it.

@@ -244,6 +244,35 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
 #define JPGE_FMT_Y210 40
 #define JPGE_FMT_P210 41
 #define JPGE_FMT_I210 42
+/* v210: the 10-bit 4:2:2 frames that SDI capture hardware writes and that QuickTime / AVI
+ * "uncompressed 10-bit" files and ffmpeg's v210 codec hold.  One plane; `rgb` points at the
+ * frame's first byte and `stride` is the row pitch in BYTES.  A row is a sequence of 32-bit
+ * little-endian words, each holding three 10-bit samples at bits 0-9, 10-19 and 20-29; bits
+ * 30-31 are never read.  The samples of a row, in word-and-field order, form the stream
+ *   Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 ...
+ * so that pixel x has its Y at stream index 2x + 1, cell c = x >> 1 its Cb at index 4c and its Cr
+ * at 4c + 2, and stream index k is field k % 3 of word k / 3.  Six pixels make a group of four
+ * words (16 bytes), and a row occupies jpge_v210_row_bytes(width) = 16 * ceil(width / 6) bytes:
+ * stride 0 means that; the conventional pitch 128 * ceil(width / 48) is one valid stride, not a
+ * requirement.  Samples of the last group beyond pixel width - 1 and its cell are storage only and
+ * never reach the output (with an odd width the last cell's Cb and Cr are real).
+ * The frame means exactly what the Y210, P210 or I210 frame of the same samples s_y, s_cb, s_cr
+ * means (above): yc = 0.25 s_y - y_off, u = 0.25 s_cb - 128, v = 0.25 s_cr - 128, the three lines
+ * of jpge_set_yuv_transform per pixel, always (JPGE_YUV_FULL_601: the identity, for its clamps),
+ * then the context's subsampling mode, the chroma edge-replicated in the chroma domain.  So
+ *   - a v210 frame gives, byte for byte, the .jpg of the Y210, P210 or I210 frame of its samples;
+ *   - a v210 frame whose samples are all multiples of 4 gives the .jpg of the 8-bit YUYV / NV16 /
+ *     I422 frame of s / 4.
+ * Accepted: all six subsampling modes (JPGE_S422 is the native one), every Huffman mode and restart
+ * interval, single frames, batches and frame sets, jpge_group_encode_batch, device and host
+ * input.  Refused with JPGE_E_ARG (or the frame's status in a batch) before anything is queued,
+ * the context staying usable: a base or stride that is not a multiple of 4, a stride below
+ * jpge_v210_row_bytes(width), maxval != 255, a non-zero plane_stride, a downscale factor above 1,
+ * jpge_stripe_transform and jpge_group_encode_striped.  The fast path needs base and stride
+ * 16-byte aligned; any other multiples of 4 work, slower.
+ * jpge_input_format_info reports bytes_per_pixel 0 for this layout: a row is not a whole number
+ * of bytes per pixel; use jpge_v210_row_bytes. */
+#define JPGE_FMT_V210 48
 /* One plane of 8-bit luminance: `height` rows of `stride` bytes (0 = width), one byte per
  * pixel; a sample v enters the transform as the value v - 128, as a Y sample above.
  * maxval must be 255 and plane_stride 0 (else JPGE_E_ARG).  The output is a baseline JPEG
@@ -269,14 +298,24 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
  * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
  * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
- * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts, the two 10-bit 4:2:0 and the three 10-bit 4:2:2 layouts and for
+ * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts, the two 10-bit 4:2:0 and the three 10-bit 4:2:2 layouts, v210 and for
  * JPGE_FMT_GRAY8 (stripes are three-component 4:2:0 of interleaved colour); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
 int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
 /* the current setting (plane_stride may be NULL) */
 int jpge_get_input_format(jpge_ctx* ctx, int* format, size_t* plane_stride);
 /* bytes per pixel along a row and number of planes of a layout (host only; either
- * pointer may be NULL); unknown layout: JPGE_E_ARG */
+ * pointer may be NULL); unknown layout: JPGE_E_ARG.  JPGE_FMT_V210: 0 bytes per pixel, meaning
+ * "not a whole number": its rows are jpge_v210_row_bytes(width) */
 int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes);
+/* Bytes of a v210 row of `width` pixels: 16 * ceil(width / 6).  Host only.  (An addition.) */
+size_t jpge_v210_row_bytes(uint32_t width);
+/* The layout rule of JPGE_FMT_V210 in plain C++ on the host: the samples of the `height` rows of
+ * pitch `stride` (0 = jpge_v210_row_bytes(width)) at `src` as planes y (height x width), cb and cr
+ * (height x ceil(width / 2)), contiguous.  A caller can produce the planes and check: the frame's
+ * .jpg is that of the I210 frame of these planes.  JPGE_E_ARG: a NULL pointer, a zero dimension,
+ * a stride below a row's bytes.  (An addition.) */
+int jpge_v210_unpack(const uint8_t* src, uint32_t width, uint32_t height, size_t stride, uint16_t* y, uint16_t* cb,
+                     uint16_t* cr);
 
 /* ---- Huffman tables of the output (an addition; replaces nothing in the reference) ----
  * JPGE_HUFF_OPTIMAL builds per-image tables as writeJPEG does (Image.cpp:888-930): the

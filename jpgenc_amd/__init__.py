@@ -40,6 +40,9 @@ _FMT_420P10 = (JPGE_FMT_P010, JPGE_FMT_I010)
 #: yuv422p10le (I422's planes, low 10 bits); host frames from pack_yuv422p10
 JPGE_FMT_Y210, JPGE_FMT_P210, JPGE_FMT_I210 = 40, 41, 42
 _FMT_422P10 = (JPGE_FMT_Y210, JPGE_FMT_P210, JPGE_FMT_I210)
+#: v210 (10-bit SDI capture; QuickTime / AVI "uncompressed 10-bit"): the same samples, three to a
+#: 32-bit word, six pixels in 16 bytes; host frames from pack_v210
+JPGE_FMT_V210 = 48
 #: 4:2:2 frames of the same samples (one Cb, Cr per horizontal pixel pair of every row): packed
 #: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 groups, NV16 (Y plane + Cb,Cr rows), I422 (three planes); host
 #: frames from pack_yuv422
@@ -72,6 +75,7 @@ EXPORTS = (
     "jpge_strerror", "jpge_version", "jpge_device_count", "jpge_open", "jpge_open_ex", "jpge_close", "jpge_set_timing",
     "jpge_get_timing", "jpge_reset_timing", "jpge_get_lanes", "jpge_set_restart_interval", "jpge_set_subsampling",
     "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info",
+    "jpge_v210_row_bytes", "jpge_v210_unpack",
     "jpge_set_huffman", "jpge_get_huffman", "jpge_standard_huffman",
     "jpge_set_yuv_transform", "jpge_get_yuv_transform", "jpge_yuv_preset",
     "jpge_set_downscale", "jpge_get_downscale", "jpge_downscaled_size", "jpge_downscale_frame",
@@ -212,6 +216,9 @@ def lib() -> ctypes.CDLL:
         L.jpge_set_input_format.argtypes = [vp, i32, sz]
         L.jpge_get_input_format.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(sz)]
         L.jpge_input_format_info.argtypes = [i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.jpge_v210_row_bytes.restype = sz
+        L.jpge_v210_row_bytes.argtypes = [u32]
+        L.jpge_v210_unpack.argtypes = [vp, u32, u32, sz, vp, vp, vp]
         L.jpge_set_huffman.argtypes = [vp, i32, ctypes.POINTER(HuffSpec)]
         L.jpge_get_huffman.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(HuffSpec)]
         L.jpge_standard_huffman.argtypes = [i32, ctypes.POINTER(HuffSpec)]
@@ -487,7 +494,8 @@ def arai_constants() -> tuple[np.ndarray, np.ndarray]:
 
 
 def input_format_info(fmt: int) -> tuple[int, int]:
-    """(bytes per pixel along a row, planes) of an input layout (JPGE_FMT_*); host only."""
+    """(bytes per pixel along a row, planes) of an input layout (JPGE_FMT_*); host only.
+    (JPGE_FMT_V210: 0 bytes per pixel, not a whole number; its rows are v210_row_bytes(w).)"""
     b, n = ctypes.c_int32(), ctypes.c_int32()
     _check(lib().jpge_input_format_info(int(fmt), ctypes.byref(b), ctypes.byref(n)), "input_format_info")
     return b.value, n.value
@@ -724,11 +732,71 @@ def pack_yuv422p10(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     return f, w, h, stride
 
 
+def v210_row_bytes(w: int) -> int:
+    """Bytes of a v210 row of w pixels: 16 * ceil(w / 6) (jpge_v210_row_bytes)."""
+    if not 0 <= int(w) <= 0xFFFFFFFF:
+        raise ValueError(f"width {w}")
+    return int(lib().jpge_v210_row_bytes(int(w)))
+
+
+def v210_unpack(frame, w: int, h: int, stride: int = 0):
+    """(y, cb, cr): the uint16 sample planes (H, W), (H, ceil(W/2)), (H, ceil(W/2)) of a host v210
+    frame of bytes, rows of pitch `stride` (0: the least one), by the layout rule of jpge.h on the
+    host (jpge_v210_unpack)."""
+    a = np.ascontiguousarray(np.asarray(frame)).reshape(-1).view(np.uint8)
+    w, h, stride = int(w), int(h), int(stride)
+    if w < 1 or h < 1 or stride < 0:
+        raise ValueError(f"a {w}x{h} frame of stride {stride}")
+    row = v210_row_bytes(w)
+    pitch = stride or row
+    if pitch < row or a.size < pitch * (h - 1) + row:
+        raise ValueError(f"{a.size} bytes do not hold {h} v210 rows of {w} pixels at stride {pitch}")
+    cw = (w + 1) // 2
+    y, cb, cr = np.empty((h, w), np.uint16), np.empty((h, cw), np.uint16), np.empty((h, cw), np.uint16)
+    _check(lib().jpge_v210_unpack(_p(a), w, h, stride, _p(y), _p(cb), _p(cr)), "v210_unpack")
+    return y, cb, cr
+
+
+def pack_v210(y: np.ndarray, cb: np.ndarray, cr: np.ndarray, stride: int = 0):
+    """(frame, w, h, stride): the (H, W) Y plane and the (H, ceil(W/2)) Cb and Cr planes of 10-bit
+    samples (integers 0..1023) as one contiguous host v210 frame of bytes, rows of pitch `stride`
+    (0: the least one, v210_row_bytes(W); else a multiple of 4 not below it).  The samples of the
+    last group beyond the frame, bits 30-31 of every word and the rows' padding are zero.  The
+    frame (a Yuv422Frame) is what encode, encode_batch, fdct_quant and symbol_stats take when the
+    input layout is JPGE_FMT_V210."""
+    y, cb, cr = (np.ascontiguousarray(p) for p in (y, cb, cr))
+    for p in (y, cb, cr):
+        if p.dtype.kind not in "ui" or (p.size and (int(p.min()) < 0 or int(p.max()) > 1023)):
+            raise ValueError("pack_v210 takes integer planes of 10-bit samples (0..1023)")
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
+    h, w = y.shape
+    cw = (w + 1) // 2
+    if cb.shape != (h, cw) or cr.shape != (h, cw):
+        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({h}, {cw}) for a {w}x{h} frame")
+    row = v210_row_bytes(w)
+    stride = int(stride) or row
+    if stride < row or stride % 4:
+        raise ValueError(f"stride {stride}: a multiple of 4, at least {row}")
+    # the row's stream Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 ..., three samples to a word
+    n = 3 * (row // 4)
+    st = np.zeros((h, n), np.uint32)
+    st[:, 1:2 * w:2] = y
+    st[:, 0:4 * cw:4] = cb
+    st[:, 2:4 * cw:4] = cr
+    buf = np.zeros((h, stride // 4), "<u4")
+    buf[:, :row // 4] = st[:, 0::3] | (st[:, 1::3] << 10) | (st[:, 2::3] << 20)
+    f = buf.reshape(-1).view(np.uint8).view(Yuv422Frame)
+    f.fmt, f.width, f.height, f.stride = JPGE_FMT_V210, w, h, stride
+    return f, w, h, stride
+
+
 def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     """(width, height, row stride in bytes) of a C-contiguous frame shaped for layout `fmt`:
     (H, W, 3), (H, W, 4) or (3, H, W); GRAY8: (H, W); NV12 and I420: a pack_yuv420 frame of
     that layout; YUYV, UYVY, NV16 and I422: a pack_yuv422 frame of that layout; P010, I010 and
-    Y210, P210, I210: a pack_yuv420p10 / pack_yuv422p10 frame of that layout.  A width or
+    Y210, P210, I210: a pack_yuv420p10 / pack_yuv422p10 frame of that layout; V210: a pack_v210
+    frame.  A width or
     height of 0 or above 65535 (a JPEG frame header's limit) is a ValueError."""
     w, h, stride = _frame_geom_any(a, fmt)
     if not (1 <= w <= 65535 and 1 <= h <= 65535):
@@ -753,6 +821,10 @@ def _frame_geom_any(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
                 a.size != yuv420p10_bytes(fmt, a.width, a.height, a.stride):
             raise ValueError(f"input layout {fmt} takes a pack_yuv420p10({fmt}, y, cb, cr) frame")
         return a.width, a.height, a.stride
+    if fmt == JPGE_FMT_V210:
+        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or a.size != a.stride * a.height:
+            raise ValueError(f"input layout {fmt} takes a pack_v210(y, cb, cr) frame")
+        return a.width, a.height, a.stride
     if fmt in _FMT_422P10:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
                 a.size != yuv422p10_bytes(fmt, a.width, a.height, a.stride):
@@ -774,7 +846,7 @@ def _as_frame(a, fmt: int):
     """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
     if fmt == JPGE_FMT_GRAY8:
         a = np.ascontiguousarray(a)  # (the type is checked, not converted: a float plane is no gray frame)
-    elif fmt not in _FMT_420 and fmt not in _FMT_422 and fmt not in _FMT_420P10 and fmt not in _FMT_422P10:
+    elif fmt not in _FMT_420 and fmt not in _FMT_422 and fmt not in _FMT_420P10 and fmt not in _FMT_422P10 and fmt != JPGE_FMT_V210:
         a = np.ascontiguousarray(a, np.uint8)
     w, h, stride = _frame_geom(a, fmt)
     return np.ascontiguousarray(a, np.uint8), w, h, stride
@@ -903,7 +975,8 @@ class Encoder:
         """Input layout of the following encodes (JPGE_FMT_*): frames are then (H, W, 3),
         (H, W, 4) or, planar, (3, H, W); GRAY8: (H, W), written as a one-component JPEG;
         NV12 and I420: pack_yuv420 frames; YUYV, UYVY, NV16 and I422: pack_yuv422 frames; P010 and
-        I010: pack_yuv420p10 frames; Y210, P210 and I210: pack_yuv422p10 frames.  plane_stride:
+        I010: pack_yuv420p10 frames; Y210, P210 and I210: pack_yuv422p10 frames; V210: pack_v210
+        frames.  plane_stride:
         bytes between the planes of the raw-pointer entries' planar frames (NV12, I420: from
         the Y plane to the chroma, as for NV16 and I422; 0 = stride * height; the packed 4:2:2
         layouts are one plane and take 0)."""
@@ -1312,6 +1385,48 @@ class Encoder:
         self.set_input_format(fmt, plane_stride)
         try:
             n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
+        finally:
+            self.set_input_format(*prev)
+        return n if host_out is None else host_out[:n].tobytes()
+
+    def encode_tensor_v210(self, t, width: int, quality: int = 50, out=None):
+        """One v210 frame (JPGE_FMT_V210: a 10-bit SDI capture buffer) of a 2-D device or host torch
+        tensor of rows, uint8 (H, bytes) or int32 (H, words), read in place through
+        jpge_encode_rgb8.  `width` is explicit: a row's length does not determine it.  ValueError
+        for what the library would refuse: another type or rank, an inner stride other than 1, a row
+        shorter than v210_row_bytes(width), a base or row pitch that is no multiple of 4, a width
+        outside 1..65535.  Every subsampling mode takes the layout (422 is the native one).
+        Returns the .jpg bytes, or, with `out` a uint8 tensor on the frame's device, writes them
+        there and returns their length.  The encoder's input layout is the same afterwards."""
+        import torch
+        if t.dtype not in (torch.uint8, torch.int32) or t.dim() != 2 or t.numel() == 0:
+            raise ValueError("encode_tensor_v210 takes a 2-D uint8 or int32 tensor of rows")
+        if t.stride(1) != 1 and t.shape[1] > 1:
+            raise ValueError(f"strides {tuple(t.stride())}: the inner dimension must have unit stride")
+        w, h, es = int(width), int(t.shape[0]), t.element_size()
+        if not 1 <= w <= 65535 or h > 65535:
+            raise ValueError(f"a {w}x{h} frame: 1..65535 each way")
+        row = v210_row_bytes(w)
+        if int(t.shape[1]) * es < row:
+            raise ValueError(f"rows of {int(t.shape[1]) * es} bytes: {w} pixels take {row}")
+        stride = es * t.stride(0) if h > 1 else row
+        if stride < row:
+            raise ValueError("rows overlap")
+        if stride % 4 or t.data_ptr() % 4:
+            raise ValueError("the base and the row pitch must be multiples of 4")
+        flags = JPGE_DEVICE_INPUT if t.is_cuda else 0
+        host_out = None
+        if out is None:
+            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            out_ptr, cap = _p(host_out), host_out.size
+        else:
+            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out: a contiguous uint8 device tensor")
+            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
+        prev = self.input_format()
+        self.set_input_format(JPGE_FMT_V210, 0)
+        try:
+            n = self.encode_ptr(t.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
         finally:
             self.set_input_format(*prev)
         return n if host_out is None else host_out[:n].tobytes()

@@ -180,7 +180,7 @@ const char* jpge_strerror(int s) {
     }
 }
 
-int jpge_version(void) { return 105; }
+int jpge_version(void) { return 106; }
 
 int jpge_device_count(int* n) {
     if (!n) return JPGE_E_ARG;
@@ -396,6 +396,32 @@ int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes) {
     if (!jpge::fmt_valid(format)) return JPGE_E_ARG;
     if (bytes_per_pixel) *bytes_per_pixel = (int)jpge::fmt_bpp(format);
     if (planes) *planes = (int)jpge::fmt_planes(format);
+    return JPGE_OK;
+}
+
+size_t jpge_v210_row_bytes(uint32_t width) { return (size_t)jpge::v210_row_bytes(width); }
+
+int jpge_v210_unpack(const uint8_t* src, uint32_t width, uint32_t height, size_t stride, uint16_t* y, uint16_t* cb,
+                     uint16_t* cr) {
+    if (!src || !y || !cb || !cr || !width || !height) return JPGE_E_ARG;
+    const size_t row = (size_t)jpge::v210_row_bytes(width);
+    if (!stride) stride = row;
+    if (stride < row) return JPGE_E_ARG;
+    const uint32_t cw = jpge::chroma_dim(width);
+    // sample k of a row's stream Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 ...: field k % 3 of word k / 3
+    auto sample = [](const uint8_t* r, size_t k) -> uint16_t {
+        const uint8_t* q = r + 4 * (k / 3);
+        const uint32_t w = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+        return (uint16_t)((w >> (10 * (k % 3))) & 0x3FF);
+    };
+    for (uint32_t j = 0; j < height; ++j) {
+        const uint8_t* r = src + (size_t)j * stride;
+        for (uint32_t x = 0; x < width; ++x) y[(size_t)j * width + x] = sample(r, 2 * (size_t)x + 1);
+        for (uint32_t c = 0; c < cw; ++c) {
+            cb[(size_t)j * cw + c] = sample(r, 4 * (size_t)c);
+            cr[(size_t)j * cw + c] = sample(r, 4 * (size_t)c + 2);
+        }
+    }
     return JPGE_OK;
 }
 

@@ -725,6 +725,8 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     if (gray && f.maxval != 255) return kErrArg;
     // 10-bit layouts: 16-bit words, so an even base and even pitches
     if (fmt_yuv10(f.fmt) && (((uintptr_t)f.rgb | f.stride | f.plane_stride) & 1)) return kErrArg;
+    // (v210: 32-bit words, so a base and a pitch that are multiples of 4)
+    if (f.fmt == kFmtV210 && (((uintptr_t)f.rgb | f.stride) & 3)) return kErrArg;
     if (gray) qc = qy;
     const size_t row = (size_t)fmt_row_bytes(f.fmt, f.width);
     const size_t stride = f.stride ? f.stride : row;
@@ -737,7 +739,9 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     // copies; I422 has I420's chroma planes with a row per pixel row; Y210, P210 and I210 are
     // to P010 and I010 what the packed layouts, NV16 and I422 are to NV12 and I420)
     const bool half = fmt_yuv420(f.fmt) || f.fmt == kFmtI422 || f.fmt == kFmtI210;
-    const size_t dev_pitch = align_up(row, f.fmt == kFmtI420 || f.fmt == kFmtI422 || f.fmt == kFmtI010 || f.fmt == kFmtI210 ? 32 : 16);
+    // (v210: its conventional pitch, rows of 48 pixels in 128 bytes)
+    const size_t dev_pitch = f.fmt == kFmtV210 ? 128 * (((size_t)f.width + 47) / 48)
+                                               : align_up(row, f.fmt == kFmtI420 || f.fmt == kFmtI422 || f.fmt == kFmtI010 || f.fmt == kFmtI210 ? 32 : 16);
     const size_t dev_plane = dev_pitch * f.height;
     const size_t crows = f.fmt == kFmtI422 || f.fmt == kFmtI210 ? f.height : chroma_dim(f.height),
                  crow = f.fmt == kFmtNv12 || f.fmt == kFmtP010 ? row : (size_t)fmt_bpp(f.fmt) * chroma_dim(f.width);  // (4:2:0 layouts, I422, I210)
@@ -756,7 +760,9 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
         // (planar: the planes one after the other, dev_pitch * height bytes each)
         if (stride == dev_pitch && (planes == 1 || plane_stride == dev_plane))
             // one linear copy (a 2D copy can fall back to a slower engine path)
-            JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, dev_bytes, hipMemcpyHostToDevice, s.stream));
+            // (v210: up to the last row's last group; a capture row's padding need not be there)
+            JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, f.fmt == kFmtV210 ? dev_bytes - dev_pitch + row : dev_bytes,
+                                    hipMemcpyHostToDevice, s.stream));
         else if (half) {
             // the Y plane, then the chroma plane(s): NV12 one of Cb,Cr pairs, I420 Cb then Cr
             JPGE_HIP(hipMemcpy2DAsync(s.d_in, dev_pitch, f.rgb, stride, (size_t)fmt_bpp(f.fmt) * f.width, f.height, hipMemcpyHostToDevice,

@@ -172,7 +172,7 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
 #define JPGE_K1_SHAPE 0
 #endif
 constexpr int kShape = JPGE_K1_SHAPE;
-static_assert(kShape >= kShapeRgb8 && kShape <= kShapeI210, "JPGE_K1_SHAPE");
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapeV210, "JPGE_K1_SHAPE");
 // The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
 // layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
 // conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
@@ -190,7 +190,12 @@ constexpr bool kGray = kShape == kShapeGray;
 // The 10-bit 4:2:2 shapes (Y210, P210, I210) stage the same ten-bit words, a cell's chroma pair in
 // both of its pixels (cell x >> 1 of the pixel's own row), and have the !kExact instance of every
 // kernel the planar 4:4:4 shape has: each mode's filter runs on the chroma-repeated frame.
-constexpr bool kTen422 = kShape == kShapeY210 || kShape == kShapeP210 || kShape == kShapeI210;
+// The v210 shape stages the same words from 32-bit words of three samples: ten-bit 4:2:2 with no
+// chroma descriptors and no plane_stride, like Y210, its samples neither the top nor the low 10
+// bits of a 16-bit word (kTenHi does not apply); its loads and its unpack depend on the lane's
+// phase ("v210" below).
+constexpr bool kV210 = kShape == kShapeV210;
+constexpr bool kTen422 = kShape == kShapeY210 || kShape == kShapeP210 || kShape == kShapeI210 || kV210;
 constexpr bool kTen = kShape == kShapeP010 || kShape == kShapeI010 || kTen422;
 constexpr bool kTenHi = kShape == kShapeP010 || kShape == kShapeP210;  // planes of words that hold a sample in their top 10 bits
 constexpr bool kYuv420 = kShape == kShapeNv12 || kShape == kShapeI420 || (kTen && !kTen422);
@@ -309,6 +314,45 @@ __device__ __forceinline__ void unpack_yuv10(const uint4& v0, const uint4& v1, c
         px[2 * cell + 1] = __builtin_amdgcn_ubfe(y[cell], 16u + lo, 10u) | cc;
     }
 }
+// v210: a row is groups of four 32-bit words (16 bytes) that hold six pixels, three samples to
+// a word at bits 0-9, 10-19, 20-29:
+//   w0 = Cb0 Y0 Cr0,  w1 = Y1 Cb1 Y2,  w2 = Cr1 Y3 Cb2,  w3 = Y4 Cr2 Y5
+// A lane's run n = xs / 16 (16 pixels = 2 2/3 groups) starts p = 16 n - 6 g0 pixels into group
+// g0 = floor(8 n / 3): with n = 3 q + r, g0 = 8 q + {0, 2, 5}[r] and p = {0, 4, 2}[r], always even,
+// so that a cell never straddles two runs.  The run lies in groups g0 .. g0 + 2 (r = 1: g0 + 3,
+// whose first cell holds its last two pixels).  r differs between the lanes of a wave.
+// The unpack is branch-free: v0..v3 are the four groups; their first 20 pixels become staged
+// words c[0..19] with compile-time words and fields, and pixel i of the run is c[i + p], chosen
+// by two selects on the lane's r.  (A lane with r != 1 has zeros in v3 and never selects them.)
+__device__ __forceinline__ void unpack_v210(const uint4& v0, const uint4& v1, const uint4& v2, const uint4& v3,
+                                            uint32_t r, uint32_t px[16]) {
+    const uint32_t w[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+    uint32_t c[24];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const uint32_t w0 = w[4 * g], w1 = w[4 * g + 1], w2 = w[4 * g + 2], w3 = w[4 * g + 3];
+        // s_cb << 10 | s_cr << 20 of the group's three cells
+        const uint32_t cc0 = ((w0 << 10) & 0x000FFC00u) | (w0 & 0x3FF00000u);
+        const uint32_t cc1 = (w1 & 0x000FFC00u) | ((w2 << 20) & 0x3FF00000u);
+        const uint32_t cc2 = ((w2 >> 10) & 0x000FFC00u) | ((w3 << 10) & 0x3FF00000u);
+        c[6 * g] = __builtin_amdgcn_ubfe(w0, 10u, 10u) | cc0;
+        c[6 * g + 1] = (w1 & 0x3FFu) | cc0;
+        c[6 * g + 2] = __builtin_amdgcn_ubfe(w1, 20u, 10u) | cc1;
+        c[6 * g + 3] = __builtin_amdgcn_ubfe(w2, 10u, 10u) | cc1;
+        c[6 * g + 4] = (w3 & 0x3FFu) | cc2;
+        c[6 * g + 5] = __builtin_amdgcn_ubfe(w3, 20u, 10u) | cc2;
+    }
+    // the selects as bit masks (all ones or zero per lane), opaque to the compiler, which
+    // otherwise turns each ternary into a divergent branch: two v_bfi_b32 per pixel
+    uint32_t m1 = r == 1 ? ~0u : 0u, m2 = r == 2 ? ~0u : 0u;
+    asm("" : "+v"(m1), "+v"(m2));
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        // (z ^ (m & (y ^ z)): the form the back end matches to v_bfi_b32 m, y, z)
+        const uint32_t a = c[i] ^ (m2 & (c[i + 2] ^ c[i]));
+        px[i] = a ^ (m1 & (c[i + 4] ^ a));  // (c[20..23] are never read)
+    }
+}
 // The gray shape's run: the load's 16 bytes, one per staged word.
 __device__ __forceinline__ void unpack_gray(const uint4& v0, uint32_t px[16]) {
     const uint32_t y[4] = {v0.x, v0.y, v0.z, v0.w};
@@ -366,7 +410,18 @@ __device__ __forceinline__ uint32_t edge_yuv(const uint8_t* base, uint64_t strid
         const uint32_t w = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
         return __builtin_amdgcn_perm(0u, w, sel4 + 2u * (sx & 1));
     }
-    if constexpr (kTen) {
+    if constexpr (kV210) {
+        // the pixel's group of four 32-bit words; sample s of the group's stream is field s % 3 of
+        // word s / 3, each word by four byte loads (any base and pitch that are multiples of 4)
+        const uint32_t g = sx / 6, k = sx - 6 * g, c = k >> 1;
+        const uint8_t* p = base + (uint64_t)sy * stride + 16 * (uint64_t)g;
+        auto sample = [p](uint32_t s) {
+            const uint8_t* q = p + 4 * (s / 3);
+            const uint32_t w = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+            return (w >> (10 * (s % 3))) & 0x3FFu;
+        };
+        return sample(2 * k + 1) | (sample(4 * c) << 10) | (sample(4 * c + 2) << 20);
+    } else if constexpr (kTen) {
         // 16-bit little-endian words, by byte loads: P010 the word's top 10 bits, Cb,Cr word
         // pairs in rows of pitch stride; I010 the low 10 bits, planes of pitch 2 * ceil(stride / 4)
         auto word = [](const uint8_t* q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8); };
@@ -437,14 +492,15 @@ __device__ __forceinline__ uint32_t edge_pixel(const uint8_t* rgb, uint64_t stri
 // inside their row, so the range is the last row's end.
 struct RgbRsrc {
     __amdgpu_buffer_rsrc_t p0;
-#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7 && JPGE_K1_SHAPE != 8 && JPGE_K1_SHAPE != 13
+#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7 && JPGE_K1_SHAPE != 8 && JPGE_K1_SHAPE != 13 && JPGE_K1_SHAPE != 16
     __amdgpu_buffer_rsrc_t p1, p2;  // (NV12, NV16: p2 repeats p1, unused)
 #endif
 };
 __device__ __forceinline__ RgbRsrc rgb_rsrc(const uint8_t* rgb, uint64_t stride, uint64_t plane_stride, uint32_t gw,
                                             uint32_t gh) {
     // (packed 4:2:2: a row is ceil(gw / 2) whole groups, of 4 bytes or, Y210, 8)
-    const int range =
+    // (v210: ceil(gw / 6) whole 16-byte groups)
+    const int range = kV210 ? (int)(uint32_t)((uint64_t)stride * (gh - 1) + 16 * (((uint64_t)gw + 5) / 6)) :
         (int)(uint32_t)((uint64_t)stride * (gh - 1) + (kPacked422 || kShape == kShapeY210 ? kBpp * 2 * (uint64_t)((gw + 1) / 2) : (uint64_t)kBpp * gw));
     uint8_t* b = const_cast<uint8_t*>(rgb);
     RgbRsrc r;
@@ -532,6 +588,12 @@ __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32
     v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 32, 0, 0));
     v3 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 48, 0, 0));
+#elif JPGE_K1_SHAPE == 16
+    // groups g0, g0 + 1, g0 + 2 at off, and at coff group g0 + 3 (a lane that does not need it: kOob)
+    v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
+    v1 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 16, 0, 0));
+    v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 32, 0, 0));
+    v3 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, coff, 0, 0));
 #elif JPGE_K1_SHAPE == 11 || JPGE_K1_SHAPE == 12 || JPGE_K1_SHAPE == 14 || JPGE_K1_SHAPE == 15
     // 32 bytes of Y; P010, P210: the 32 bytes of Cb,Cr pairs under them; I010, I210: 16 bytes of each plane
     v0 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off, 0, 0));
@@ -736,7 +798,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210)) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210 && !kV210)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -825,10 +887,19 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kShape == kShapeNv12 ? 16 : 8));
             coff = ok ? cbase + lane_coff : kOob;
         }
-        if constexpr (kTen) {
+        if constexpr (kTen && !kV210) {
             // (I010: the run's 8 cells are the 16 bytes themselves, inside their row whenever the run is)
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * kCRows) * cpitch + (uint64_t)mcol0 * kCellRun);
             coff = ok ? cbase + lane_coff : kOob;
+        }
+        if constexpr (kV210) {
+            // the run's groups ("v210" above).  Its last pixel xs + 15 <= gw - 1 lies in group
+            // (xs + 15) / 6 <= (gw - 1) / 6, the row's last, so every group a lane needs is inside
+            // the row whenever the run is; the fourth load of a lane that needs three moves nothing.
+            const uint32_t n = xs >> 4, g0 = (8 * n) / 3;
+            const uint32_t o = (uint32_t)((uint64_t)(mrow * 16) * stride_) + (uint32_t)r16 * (uint32_t)stride_ + 16 * g0;
+            load_run(rgb_rs, ok ? o : kOob, ok && n % 3 == 1 ? o + 48 : kOob, v0, v1, v2, v3);
+            return ok;
         }
         if constexpr (kPlanes422) {
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 16) * cpitch + (uint64_t)mcol0 * (kPairs ? 16 : 8));
@@ -1022,6 +1093,8 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         if constexpr (kDs > 1) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) px[i] = nx[i];
+        } else if constexpr (kV210) {
+            unpack_v210(c0, c1, c2, c3, (xs >> 4) % 3, px);
         } else if constexpr (kTen) {
             unpack_yuv10(c0, c1, c2, c3, px);
         } else if constexpr (kYuv420 || kPlanes422) {
@@ -1163,7 +1236,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
     }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
-    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210)) {
+    if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210 && !kV210)) {
         ps_ = a.plane_stride;
         asm volatile("" : "+s"(ps_));
     }
@@ -1236,10 +1309,17 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kPairs ? 8 : 4) * kYh);
             coff = ok ? cbase + lane_coff : kOob;
         }
-        if constexpr (kTen) {
+        if constexpr (kTen && !kV210) {
             // (I210: the run's 8 cells are the 16 bytes themselves, inside their row whenever the run is)
             const uint32_t cbase = (uint32_t)((uint64_t)(mrow * 8) * cpitch + (uint64_t)mcol0 * (kCellRun / 2) * kYh);
             coff = ok ? cbase + lane_coff : kOob;
+        }
+        if constexpr (kV210) {
+            // (as in fdct_kernel: xs = 16 n with n = 8 * tile column + c8)
+            const uint32_t n = xs >> 4, g0 = (8 * n) / 3;
+            const uint32_t o = (uint32_t)((uint64_t)(mrow * 8) * stride_) + (uint32_t)r8 * (uint32_t)stride_ + 16 * g0;
+            load_run(rgb_rs, ok ? o : kOob, ok && n % 3 == 1 ? o + 48 : kOob, v0, v1, v2, v3);
+            return ok;
         }
         load_run(rgb_rs, off, coff, v0, v1, v2, v3);
         return ok;
@@ -1308,6 +1388,8 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
             for (int i = 0; i < 16; ++i) px[i] = nx[i];
         } else if constexpr (kGray) {
             unpack_gray(c0, px);
+        } else if constexpr (kV210) {
+            unpack_v210(c0, c1, c2, c3, (xs >> 4) % 3, px);
         } else if constexpr (kTen) {
             unpack_yuv10(c0, c1, c2, c3, px);
         } else if constexpr (kPlanes422) {
@@ -1519,7 +1601,7 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
 
 #if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1
 // this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
-// _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...)
+// _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210 / _v210; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
@@ -1552,6 +1634,8 @@ hipError_t launch_fdct_i210(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid
 hipError_t launch_fdct_y210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_p210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_i210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_v210(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_v210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 // the downscaling builds (FdctArgs::ds 2, 4) of the shapes that have them
 hipError_t launch_fdct_rgb8_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_rgb8_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
@@ -1604,6 +1688,8 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
             return hipErrorInvalidValue;
         // 10-bit layouts: 16-bit words (even addresses and pitches), and always the sample transform
         if (fmt_yuv10(m.fmt) && ((((uintptr_t)m.rgb | m.stride | m.plane_stride) & 1) || !m.xf_on)) return hipErrorInvalidValue;
+        // (v210: 32-bit words, one plane, no downscaling build)
+        if (m.fmt == kFmtV210 && ((((uintptr_t)m.rgb | m.stride) & 3) || m.plane_stride)) return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
             fmt_shape(m.fmt) != fmt_shape(a.fmt) || (m.xf_on != 0) != (a.xf_on != 0) ||
             m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs, m.ds))
@@ -1617,6 +1703,7 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         if (fmt_shape(a.fmt) == kShapeY210) return launch_fdct_y210_one(fs, grid, s, t);
         if (fmt_shape(a.fmt) == kShapeP210) return launch_fdct_p210_one(fs, grid, s, t);
         if (fmt_shape(a.fmt) == kShapeI210) return launch_fdct_i210_one(fs, grid, s, t);
+        if (fmt_shape(a.fmt) == kShapeV210) return launch_fdct_v210_one(fs, grid, s, t);
     }
     // the other load shapes have the frame-set instance only (a lone frame is a set of one)
     FrameSet<FdctArgs, kMaxSet> w{};
@@ -1648,6 +1735,7 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         case kShapeY210: return launch_fdct_y210(w, grid, s, t);
         case kShapeP210: return launch_fdct_p210(w, grid, s, t);
         case kShapeI210: return launch_fdct_i210(w, grid, s, t);
+        case kShapeV210: return launch_fdct_v210(w, grid, s, t);
         default: return launch_fdct_planar(w, grid, s, t);
     }
 }

@@ -74,18 +74,22 @@ constexpr int kFmtP010 = 32, kFmtI010 = 33;
 // planes, top 10 bits), I210 (I422's planes, low 10 bits).  A frame is the frame of samples
 // s_y[y][x], s_cb[y][x >> 1], s_cr[y][x >> 1], each s / 4, in every subsampling mode.
 constexpr int kFmtY210 = 40, kFmtP210 = 41, kFmtI210 = 42;
+// v210 (10-bit SDI capture): the same samples packed three to a little-endian 32-bit word (bits
+// 0-9, 10-19, 20-29), a row the stream Cb0 Y0 Cr0 Y1 Cb1 Y2 Cr1 Y3 ...: pixel x has its Y at stream
+// index 2x + 1, cell c its Cb at 4c and its Cr at 4c + 2; six pixels are a group of four words.
+constexpr int kFmtV210 = 48;
 // one plane of 8-bit luminance samples (a sample v is the fp64 value v - 128, as a Y sample
 // above): a one-component stream, Geometry::gray(), whatever the subsampling mode
 constexpr int kFmtGray8 = 8;
 JPGE_HD inline bool fmt_valid(int fmt) {
     return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar) ||
            (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt == kFmtP010 || fmt == kFmtI010 ||
-           (fmt >= kFmtY210 && fmt <= kFmtI210);
+           (fmt >= kFmtY210 && fmt <= kFmtI210) || fmt == kFmtV210;
 }
 JPGE_HD inline bool fmt_gray(int fmt) { return fmt == kFmtGray8; }
 JPGE_HD inline bool fmt_yuv(int fmt) { return fmt >= kFmtNv12; }
-JPGE_HD inline bool fmt_yuv422p10(int fmt) { return fmt >= kFmtY210 && fmt <= kFmtI210; }  // 10-bit, chroma at half width, every row
-JPGE_HD inline bool fmt_yuv10(int fmt) { return fmt == kFmtP010 || fmt == kFmtI010 || fmt_yuv422p10(fmt); }  // 16-bit words of 10-bit samples
+JPGE_HD inline bool fmt_yuv422p10(int fmt) { return (fmt >= kFmtY210 && fmt <= kFmtI210) || fmt == kFmtV210; }  // 10-bit, chroma at half width, every row
+JPGE_HD inline bool fmt_yuv10(int fmt) { return fmt == kFmtP010 || fmt == kFmtI010 || fmt_yuv422p10(fmt); }  // 10-bit samples (in 16-bit words; v210: three to a 32-bit word)
 JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420 || fmt == kFmtP010 || fmt == kFmtI010; }  // chroma planes at half size
 JPGE_HD inline bool fmt_yuv422(int fmt) { return (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt_yuv422p10(fmt); }  // chroma at half width, every row
 JPGE_HD inline bool fmt_packed422(int fmt) { return fmt == kFmtYuyv || fmt == kFmtUyvy; }  // (8-bit: 4-byte groups)
@@ -105,19 +109,24 @@ constexpr int kShapeI010 = 12;   // 32 Y bytes + the 16 Cb bytes + the 16 Cr byt
 constexpr int kShapeY210 = 13;   // the run's 64 bytes (8 groups of four words): four b128 loads
 constexpr int kShapeP210 = 14;   // the P010 shape's four loads, the Cb,Cr row that of the pixels
 constexpr int kShapeI210 = 15;   // the I010 shape's four loads, the chroma rows those of the pixels
+constexpr int kShapeV210 = 16;   // the three or four 16-byte groups that hold the run: four b128 loads, a per-lane phase
 JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt == kFmtY210 ? kShapeY210 : fmt == kFmtP210 ? kShapeP210 : fmt == kFmtI210 ? kShapeI210 : fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
+    return fmt == kFmtV210 ? kShapeV210 : fmt == kFmtY210 ? kShapeY210 : fmt == kFmtP210 ? kShapeP210 : fmt == kFmtI210 ? kShapeI210 : fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
          : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
 }
 // bytes per pixel within a row (planar: of one plane), and planes
-JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt_packed422(fmt) || fmt_yuv10(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
-JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) || fmt == kFmtY210 ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 || fmt == kFmtP010 || fmt == kFmtP210 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
+// (v210: 0, a row is no whole number of bytes per pixel; fmt_row_bytes has its rows)
+JPGE_HD inline uint64_t v210_row_bytes(uint32_t width) { return 16 * (((uint64_t)width + 5) / 6); }
+JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtV210 ? 0u : fmt_packed422(fmt) || fmt_yuv10(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
+JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) || fmt == kFmtY210 || fmt == kFmtV210 ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 || fmt == kFmtP010 || fmt == kFmtP210 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
 // The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
 // that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs; NV16 likewise; the packed
-// 4:2:2 layouts: ceil(width / 2) whole 4-byte groups; Y210: whole 8-byte groups).
+// 4:2:2 layouts: ceil(width / 2) whole 4-byte groups; Y210: whole 8-byte groups; v210: ceil(width / 6)
+// whole 16-byte groups).
 JPGE_HD inline uint64_t fmt_row_bytes(int fmt, uint32_t width) {
     if (fmt_packed422(fmt)) return 4 * (((uint64_t)width + 1) / 2);
     if (fmt == kFmtY210) return 8 * (((uint64_t)width + 1) / 2);
+    if (fmt == kFmtV210) return v210_row_bytes(width);
     if (fmt == kFmtP010 || fmt == kFmtP210) return 2 * (((uint64_t)width + 1) & ~(uint64_t)1);  // (16-bit words; I010, I210: 2 * width, by fmt_bpp)
     return fmt == kFmtNv12 || fmt == kFmtNv16 ? ((uint64_t)width + 1) & ~(uint64_t)1 : (uint64_t)fmt_bpp(fmt) * width;
 }

@@ -15,6 +15,7 @@ import ctypes
 import os
 import weakref
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -29,17 +30,14 @@ JPGE_FMT_RGB8, JPGE_FMT_BGR8, JPGE_FMT_RGBA8, JPGE_FMT_BGRA8, JPGE_FMT_RGB8_PLAN
 #: full-range 8-bit Y, Cb, Cr frames (no colour conversion): NV12 and I420 (chroma at half size;
 #: host frames from pack_yuv420), and planar (3, H, W)
 JPGE_FMT_NV12, JPGE_FMT_I420, JPGE_FMT_YUV444_PLANAR = 16, 17, 18
-_FMT_420 = (JPGE_FMT_NV12, JPGE_FMT_I420)
 #: 10-bit 4:2:0 frames of little-endian 16-bit words (jpge.h): P010 (NV12's planes, a sample in its
 #: word's top 10 bits) and I010 / yuv420p10le (I420's planes, a sample in the low 10 bits); a
 #: sample s enters the sample transform as s / 4, unrounded
 JPGE_FMT_P010, JPGE_FMT_I010 = 32, 33
-_FMT_420P10 = (JPGE_FMT_P010, JPGE_FMT_I010)
 #: 10-bit 4:2:2 frames of the same words (one Cb, Cr per horizontal pixel pair of every row): Y210
 #: (packed groups Y0 Cb Y1 Cr, top 10 bits), P210 (NV16's planes, top 10 bits) and I210 /
 #: yuv422p10le (I422's planes, low 10 bits); host frames from pack_yuv422p10
 JPGE_FMT_Y210, JPGE_FMT_P210, JPGE_FMT_I210 = 40, 41, 42
-_FMT_422P10 = (JPGE_FMT_Y210, JPGE_FMT_P210, JPGE_FMT_I210)
 #: v210 (10-bit SDI capture; QuickTime / AVI "uncompressed 10-bit"): the same samples, three to a
 #: 32-bit word, six pixels in 16 bytes; host frames from pack_v210
 JPGE_FMT_V210 = 48
@@ -47,7 +45,6 @@ JPGE_FMT_V210 = 48
 #: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 groups, NV16 (Y plane + Cb,Cr rows), I422 (three planes); host
 #: frames from pack_yuv422
 JPGE_FMT_YUYV, JPGE_FMT_UYVY, JPGE_FMT_NV16, JPGE_FMT_I422 = 20, 21, 22, 23
-_FMT_422 = (JPGE_FMT_YUYV, JPGE_FMT_UYVY, JPGE_FMT_NV16, JPGE_FMT_I422)
 #: one (H, W) plane of 8-bit luminance -> a one-component (grayscale) JPEG; no chroma: the
 #: chroma table and the subsampling mode do not enter
 JPGE_FMT_GRAY8 = 8
@@ -525,8 +522,8 @@ def _huff_specs(specs):
 
 
 class Yuv420Frame(np.ndarray):
-    """A host NV12 or I420 frame (pack_yuv420): the layout's bytes, planes back to back
-    (plane stride 0), with the geometry that a flat buffer does not show."""
+    """A host NV12, I420, P010 or I010 frame (pack_yuv420, pack_yuv420p10): the layout's bytes,
+    planes back to back (plane stride 0), with the geometry that a flat buffer does not show."""
     fmt = width = height = stride = None
 
     def __array_finalize__(self, obj):
@@ -534,15 +531,116 @@ class Yuv420Frame(np.ndarray):
             setattr(self, k, getattr(obj, k, None))
 
 
+class Yuv422Frame(Yuv420Frame):
+    """A host 4:2:2 frame (pack_yuv422, pack_yuv422p10, pack_v210): the layout's bytes, planes back
+    to back (plane stride 0), with the geometry that a flat buffer does not show."""
+
+
+class _Yuv(NamedTuple):
+    """A Y, Cb, Cr layout with half-width chroma, as jpge.h states it."""
+    family: str  # pack_<family> builds its host frames, <family>_bytes sizes them
+    size: int    # bytes per sample: 1, or 2 (a little-endian word)
+    shift: int   # the sample's lowest bit inside its word
+    vsub: int    # picture rows per chroma row: 2 (ceil(h / 2) chroma rows; a Yuv420Frame) or 1 (a Yuv422Frame)
+    order: str   # "planar" Y, Cb, Cr planes; "semi": a Y plane + rows of Cb,Cr pairs; groups "yuyv" or "uyvy"
+
+
+#: the one statement of these layouts on the Python side: the byte counts, the host packers, the
+#: frame check and the plane geometry of the encode_tensor_yuv* methods all read it (v210 keeps
+#: its own row rule, v210_row_bytes; the RGB layouts, GRAY8 and YUV444_PLANAR: input_format_info)
+_YUV = {
+    JPGE_FMT_NV12: _Yuv("yuv420", 1, 0, 2, "semi"), JPGE_FMT_I420: _Yuv("yuv420", 1, 0, 2, "planar"),
+    JPGE_FMT_P010: _Yuv("yuv420p10", 2, 6, 2, "semi"), JPGE_FMT_I010: _Yuv("yuv420p10", 2, 0, 2, "planar"),
+    JPGE_FMT_YUYV: _Yuv("yuv422", 1, 0, 1, "yuyv"), JPGE_FMT_UYVY: _Yuv("yuv422", 1, 0, 1, "uyvy"),
+    JPGE_FMT_NV16: _Yuv("yuv422", 1, 0, 1, "semi"), JPGE_FMT_I422: _Yuv("yuv422", 1, 0, 1, "planar"),
+    JPGE_FMT_Y210: _Yuv("yuv422p10", 2, 6, 1, "yuyv"), JPGE_FMT_P210: _Yuv("yuv422p10", 2, 6, 1, "semi"),
+    JPGE_FMT_I210: _Yuv("yuv422p10", 2, 0, 1, "planar"),
+}
+
+
+def _yuv_layout(fmt: int, family: str) -> _Yuv:
+    L = _YUV.get(fmt)
+    if L is None or L.family != family:
+        raise ValueError(f"input layout {fmt} is not one of pack_{family}'s")
+    return L
+
+
+def _yuv_least_stride(L: _Yuv, w: int) -> int:
+    """Least row pitch in bytes: w samples, or ceil(w / 2) Cb,Cr pairs or four-sample groups."""
+    cw = (w + 1) // 2
+    return L.size * (w if L.order == "planar" else 2 * cw if L.order == "semi" else 4 * cw)
+
+
+def _yuv_chroma_stride(L: _Yuv, stride: int) -> int:
+    """Chroma row pitch for Y rows at `stride`: Cb,Cr pairs keep it; Cb and Cr planes halve it,
+    rounded up to whole samples ((stride + 1) / 2 bytes, or 2 * ceil(stride / 4))."""
+    return stride if L.order == "semi" else L.size * -(-stride // (2 * L.size))
+
+
+def _yuv_bytes(L: _Yuv, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of a frame with plane stride 0 (stride 0: the least one)."""
+    stride = stride or _yuv_least_stride(L, w)
+    if L.order in ("yuyv", "uyvy"):
+        return stride * h
+    return stride * h + (1 if L.order == "semi" else 2) * _yuv_chroma_stride(L, stride) * -(-h // L.vsub)
+
+
 def yuv420_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
     """Bytes of an NV12 or I420 frame with plane stride 0 (stride 0: the least one)."""
-    cw, ch = (w + 1) // 2, (h + 1) // 2
-    if fmt == JPGE_FMT_NV12:
-        return (stride or 2 * cw) * (h + ch)
-    if fmt == JPGE_FMT_I420:
-        stride = stride or w
-        return stride * h + 2 * ((stride + 1) // 2) * ch
-    raise ValueError(f"input layout {fmt} is not a 4:2:0 one")
+    return _yuv_bytes(_yuv_layout(fmt, "yuv420"), w, h, stride)
+
+
+def yuv420p10_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of a P010 or I010 frame with plane stride 0 (stride, in bytes, 0: the least one)."""
+    return _yuv_bytes(_yuv_layout(fmt, "yuv420p10"), w, h, stride)
+
+
+def yuv422_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of a YUYV, UYVY, NV16 or I422 frame with plane stride 0 (stride 0: the least one)."""
+    return _yuv_bytes(_yuv_layout(fmt, "yuv422"), w, h, stride)
+
+
+def yuv422p10_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
+    """Bytes of a Y210, P210 or I210 frame with plane stride 0 (stride, in bytes, 0: the least one)."""
+    return _yuv_bytes(_yuv_layout(fmt, "yuv422p10"), w, h, stride)
+
+
+def _sample_planes(name: str, y, cb, cr, vsub: int, ten_bit: bool):
+    """(y, cb, cr, w, h, cw) of a pack_* call's planes, contiguous: an (H, W) Y plane and
+    (ceil(H / vsub), ceil(W / 2)) Cb and Cr planes, converted to uint8, or, ten_bit, integers
+    0..1023 as they came."""
+    y, cb, cr = (np.ascontiguousarray(p, None if ten_bit else np.uint8) for p in (y, cb, cr))
+    for p in (y, cb, cr):
+        if ten_bit and (p.dtype.kind not in "ui" or (p.size and (int(p.min()) < 0 or int(p.max()) > 1023))):
+            raise ValueError(f"{name} takes integer planes of 10-bit samples (0..1023)")
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
+    h, w = y.shape
+    cw, ch = (w + 1) // 2, -(-h // vsub)
+    if cb.shape != (ch, cw) or cr.shape != (ch, cw):
+        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({ch}, {cw}) for a {w}x{h} frame")
+    return y, cb, cr, w, h, cw
+
+
+def _pack_yuv(family: str, fmt: int, y, cb, cr):
+    L = _yuv_layout(fmt, family)
+    y, cb, cr, w, h, cw = _sample_planes(f"pack_{family}", y, cb, cr, L.vsub, L.size == 2)
+    dt = np.uint8 if L.size == 1 else "<u2"
+    y, cb, cr = (p.astype(dt) << L.shift for p in (y, cb, cr))
+    if L.order == "planar":
+        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
+    elif L.order == "semi":
+        buf = np.zeros((h + len(cb), 2 * cw), dt)  # (odd width: one pad sample per Y row)
+        buf[:h, :w] = y
+        buf[h:, 0::2], buf[h:, 1::2] = cb, cr
+    else:
+        yo, co = (0, 1) if L.order == "yuyv" else (1, 0)
+        buf = np.zeros((h, cw, 4), dt)  # (odd width: the last group's second Y sample stays 0)
+        buf[:, :, yo], buf[:, :w // 2, yo + 2] = y[:, 0::2], y[:, 1::2]
+        buf[:, :, co], buf[:, :, co + 2] = cb, cr
+    f = buf.reshape(-1).view(np.uint8).view(Yuv420Frame if L.vsub == 2 else Yuv422Frame)
+    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, _yuv_least_stride(L, w)
+    return f, w, h, f.stride
 
 
 def pack_yuv420(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
@@ -550,39 +648,7 @@ def pack_yuv420(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     as one contiguous host frame in layout JPGE_FMT_NV12 or JPGE_FMT_I420 with the least
     stride and plane stride 0 (jpge.h).  The frame (a Yuv420Frame) is what encode,
     encode_batch, fdct_quant and symbol_stats take when the input layout is `fmt`."""
-    y, cb, cr = (np.ascontiguousarray(p, np.uint8) for p in (y, cb, cr))
-    if y.ndim != 2 or y.size == 0:
-        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
-    h, w = y.shape
-    cw, ch = (w + 1) // 2, (h + 1) // 2
-    if cb.shape != (ch, cw) or cr.shape != (ch, cw):
-        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({ch}, {cw}) for a {w}x{h} frame")
-    if fmt == JPGE_FMT_NV12:
-        stride = 2 * cw
-        buf = np.zeros((h + ch, stride), np.uint8)  # (odd width: one pad byte per Y row)
-        buf[:h, :w] = y
-        buf[h:, 0::2] = cb
-        buf[h:, 1::2] = cr
-        buf = buf.reshape(-1)
-    elif fmt == JPGE_FMT_I420:
-        stride = w  # chroma pitch (w + 1) / 2 = cw
-        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
-    else:
-        raise ValueError(f"input layout {fmt} is not a 4:2:0 one")
-    f = buf.view(Yuv420Frame)
-    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
-    return f, w, h, stride
-
-
-def yuv420p10_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
-    """Bytes of a P010 or I010 frame with plane stride 0 (stride, in bytes, 0: the least one)."""
-    cw, ch = (w + 1) // 2, (h + 1) // 2
-    if fmt == JPGE_FMT_P010:
-        return (stride or 4 * cw) * (h + ch)
-    if fmt == JPGE_FMT_I010:
-        stride = stride or 2 * w
-        return stride * h + 2 * (2 * ((stride + 3) // 4)) * ch
-    raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:0 one")
+    return _pack_yuv("yuv420", fmt, y, cb, cr)
 
 
 def pack_yuv420p10(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
@@ -591,50 +657,7 @@ def pack_yuv420p10(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     JPGE_FMT_P010 (each sample in its word's top 10 bits, the low six zero) or JPGE_FMT_I010 with
     the least stride and plane stride 0 (jpge.h).  The frame (a Yuv420Frame) is what encode,
     encode_batch, fdct_quant and symbol_stats take when the input layout is `fmt`."""
-    y, cb, cr = (np.ascontiguousarray(p) for p in (y, cb, cr))
-    for p in (y, cb, cr):
-        if p.dtype.kind not in "ui" or (p.size and (int(p.min()) < 0 or int(p.max()) > 1023)):
-            raise ValueError("pack_yuv420p10 takes integer planes of 10-bit samples (0..1023)")
-    y, cb, cr = (p.astype("<u2") for p in (y, cb, cr))
-    if y.ndim != 2 or y.size == 0:
-        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
-    h, w = y.shape
-    cw, ch = (w + 1) // 2, (h + 1) // 2
-    if cb.shape != (ch, cw) or cr.shape != (ch, cw):
-        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({ch}, {cw}) for a {w}x{h} frame")
-    if fmt == JPGE_FMT_P010:
-        stride = 4 * cw
-        buf = np.zeros((h + ch, 2 * cw), "<u2")  # (odd width: one pad word per Y row)
-        buf[:h, :w] = y << 6
-        buf[h:, 0::2] = cb << 6
-        buf[h:, 1::2] = cr << 6
-        buf = buf.reshape(-1)
-    elif fmt == JPGE_FMT_I010:
-        stride = 2 * w  # chroma pitch 2 * ceil(2 w / 4) = 2 * cw
-        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
-    else:
-        raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:0 one")
-    f = buf.view(np.uint8).view(Yuv420Frame)
-    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
-    return f, w, h, stride
-
-
-class Yuv422Frame(Yuv420Frame):
-    """A host YUYV, UYVY, NV16 or I422 frame (pack_yuv422): the layout's bytes, planes back to
-    back (plane stride 0), with the geometry that a flat buffer does not show."""
-
-
-def yuv422_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
-    """Bytes of a YUYV, UYVY, NV16 or I422 frame with plane stride 0 (stride 0: the least one)."""
-    cw = (w + 1) // 2
-    if fmt in (JPGE_FMT_YUYV, JPGE_FMT_UYVY):
-        return (stride or 4 * cw) * h
-    if fmt == JPGE_FMT_NV16:
-        return (stride or 2 * cw) * 2 * h
-    if fmt == JPGE_FMT_I422:
-        stride = stride or w
-        return stride * h + 2 * ((stride + 1) // 2) * h
-    raise ValueError(f"input layout {fmt} is not a 4:2:2 one")
+    return _pack_yuv("yuv420p10", fmt, y, cb, cr)
 
 
 def pack_yuv422(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
@@ -643,50 +666,7 @@ def pack_yuv422(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     and plane stride 0 (jpge.h).  The frame (a Yuv422Frame) is what encode, encode_batch,
     fdct_quant and symbol_stats take when the input layout is `fmt`.  (Odd width: the last
     group's second Y byte, and NV16's pad byte per Y row, are 0.)"""
-    y, cb, cr = (np.ascontiguousarray(p, np.uint8) for p in (y, cb, cr))
-    if y.ndim != 2 or y.size == 0:
-        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
-    h, w = y.shape
-    cw = (w + 1) // 2
-    if cb.shape != (h, cw) or cr.shape != (h, cw):
-        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({h}, {cw}) for a {w}x{h} frame")
-    if fmt in (JPGE_FMT_YUYV, JPGE_FMT_UYVY):
-        stride = 4 * cw
-        y2 = np.zeros((h, 2 * cw), np.uint8)
-        y2[:, :w] = y
-        buf = np.zeros((h, cw, 4), np.uint8)
-        yo, co = (0, 1) if fmt == JPGE_FMT_YUYV else (1, 0)
-        buf[:, :, yo], buf[:, :, yo + 2] = y2[:, 0::2], y2[:, 1::2]
-        buf[:, :, co], buf[:, :, co + 2] = cb, cr
-        buf = buf.reshape(-1)
-    elif fmt == JPGE_FMT_NV16:
-        stride = 2 * cw
-        buf = np.zeros((2 * h, stride), np.uint8)
-        buf[:h, :w] = y
-        buf[h:, 0::2] = cb
-        buf[h:, 1::2] = cr
-        buf = buf.reshape(-1)
-    elif fmt == JPGE_FMT_I422:
-        stride = w  # chroma pitch (w + 1) / 2 = cw
-        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
-    else:
-        raise ValueError(f"input layout {fmt} is not a 4:2:2 one")
-    f = buf.view(Yuv422Frame)
-    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
-    return f, w, h, stride
-
-
-def yuv422p10_bytes(fmt: int, w: int, h: int, stride: int = 0) -> int:
-    """Bytes of a Y210, P210 or I210 frame with plane stride 0 (stride, in bytes, 0: the least one)."""
-    cw = (w + 1) // 2
-    if fmt == JPGE_FMT_Y210:
-        return (stride or 8 * cw) * h
-    if fmt == JPGE_FMT_P210:
-        return (stride or 4 * cw) * 2 * h
-    if fmt == JPGE_FMT_I210:
-        stride = stride or 2 * w
-        return stride * h + 2 * (2 * ((stride + 3) // 4)) * h
-    raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:2 one")
+    return _pack_yuv("yuv422", fmt, y, cb, cr)
 
 
 def pack_yuv422p10(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
@@ -696,40 +676,7 @@ def pack_yuv422p10(fmt: int, y: np.ndarray, cb: np.ndarray, cr: np.ndarray):
     with the least stride and plane stride 0 (jpge.h).  The frame (a Yuv422Frame) is what encode,
     encode_batch, fdct_quant and symbol_stats take when the input layout is `fmt`.  (Odd width:
     the last group's second Y word, and P210's pad word per Y row, are 0.)"""
-    y, cb, cr = (np.ascontiguousarray(p) for p in (y, cb, cr))
-    for p in (y, cb, cr):
-        if p.dtype.kind not in "ui" or (p.size and (int(p.min()) < 0 or int(p.max()) > 1023)):
-            raise ValueError("pack_yuv422p10 takes integer planes of 10-bit samples (0..1023)")
-    y, cb, cr = (p.astype("<u2") for p in (y, cb, cr))
-    if y.ndim != 2 or y.size == 0:
-        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
-    h, w = y.shape
-    cw = (w + 1) // 2
-    if cb.shape != (h, cw) or cr.shape != (h, cw):
-        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({h}, {cw}) for a {w}x{h} frame")
-    if fmt == JPGE_FMT_Y210:
-        stride = 8 * cw
-        y2 = np.zeros((h, 2 * cw), "<u2")
-        y2[:, :w] = y
-        buf = np.zeros((h, cw, 4), "<u2")
-        buf[:, :, 0], buf[:, :, 2] = y2[:, 0::2] << 6, y2[:, 1::2] << 6
-        buf[:, :, 1], buf[:, :, 3] = cb << 6, cr << 6
-        buf = buf.reshape(-1)
-    elif fmt == JPGE_FMT_P210:
-        stride = 4 * cw
-        buf = np.zeros((2 * h, 2 * cw), "<u2")  # (odd width: one pad word per Y row)
-        buf[:h, :w] = y << 6
-        buf[h:, 0::2] = cb << 6
-        buf[h:, 1::2] = cr << 6
-        buf = buf.reshape(-1)
-    elif fmt == JPGE_FMT_I210:
-        stride = 2 * w  # chroma pitch 2 * ceil(2 w / 4) = 2 * cw
-        buf = np.concatenate([y.reshape(-1), cb.reshape(-1), cr.reshape(-1)])
-    else:
-        raise ValueError(f"input layout {fmt} is not a 10-bit 4:2:2 one")
-    f = buf.view(np.uint8).view(Yuv422Frame)
-    f.fmt, f.width, f.height, f.stride = int(fmt), w, h, stride
-    return f, w, h, stride
+    return _pack_yuv("yuv422p10", fmt, y, cb, cr)
 
 
 def v210_row_bytes(w: int) -> int:
@@ -764,16 +711,7 @@ def pack_v210(y: np.ndarray, cb: np.ndarray, cr: np.ndarray, stride: int = 0):
     last group beyond the frame, bits 30-31 of every word and the rows' padding are zero.  The
     frame (a Yuv422Frame) is what encode, encode_batch, fdct_quant and symbol_stats take when the
     input layout is JPGE_FMT_V210."""
-    y, cb, cr = (np.ascontiguousarray(p) for p in (y, cb, cr))
-    for p in (y, cb, cr):
-        if p.dtype.kind not in "ui" or (p.size and (int(p.min()) < 0 or int(p.max()) > 1023)):
-            raise ValueError("pack_v210 takes integer planes of 10-bit samples (0..1023)")
-    if y.ndim != 2 or y.size == 0:
-        raise ValueError(f"Y plane of shape {y.shape}: (H, W)")
-    h, w = y.shape
-    cw = (w + 1) // 2
-    if cb.shape != (h, cw) or cr.shape != (h, cw):
-        raise ValueError(f"chroma planes of shapes {cb.shape}, {cr.shape}: ({h}, {cw}) for a {w}x{h} frame")
+    y, cb, cr, w, h, cw = _sample_planes("pack_v210", y, cb, cr, 1, True)
     row = v210_row_bytes(w)
     stride = int(stride) or row
     if stride < row or stride % 4:
@@ -811,29 +749,14 @@ def _frame_geom_any(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
             raise ValueError(f"frame of shape {a.shape} and type {a.dtype}: input layout {fmt} (GRAY8) takes "
                              "a non-empty (H, W) uint8 array")
         return a.shape[1], a.shape[0], a.shape[1]
-    if fmt in _FMT_420:
+    if fmt in _YUV:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
-                a.size != yuv420_bytes(fmt, a.width, a.height, a.stride):
-            raise ValueError(f"input layout {fmt} takes a pack_yuv420({fmt}, y, cb, cr) frame")
-        return a.width, a.height, a.stride
-    if fmt in _FMT_420P10:
-        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
-                a.size != yuv420p10_bytes(fmt, a.width, a.height, a.stride):
-            raise ValueError(f"input layout {fmt} takes a pack_yuv420p10({fmt}, y, cb, cr) frame")
+                a.size != _yuv_bytes(_YUV[fmt], a.width, a.height, a.stride):
+            raise ValueError(f"input layout {fmt} takes a pack_{_YUV[fmt].family}({fmt}, y, cb, cr) frame")
         return a.width, a.height, a.stride
     if fmt == JPGE_FMT_V210:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or a.size != a.stride * a.height:
             raise ValueError(f"input layout {fmt} takes a pack_v210(y, cb, cr) frame")
-        return a.width, a.height, a.stride
-    if fmt in _FMT_422P10:
-        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
-                a.size != yuv422p10_bytes(fmt, a.width, a.height, a.stride):
-            raise ValueError(f"input layout {fmt} takes a pack_yuv422p10({fmt}, y, cb, cr) frame")
-        return a.width, a.height, a.stride
-    if fmt in _FMT_422:
-        if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
-                a.size != yuv422_bytes(fmt, a.width, a.height, a.stride):
-            raise ValueError(f"input layout {fmt} takes a pack_yuv422({fmt}, y, cb, cr) frame")
         return a.width, a.height, a.stride
     want = "(3, H, W)" if planes == 3 else f"(H, W, {bpp})"
     if a.ndim != 3 or (a.shape[0] != 3 if planes == 3 else a.shape[2] != bpp):
@@ -846,7 +769,7 @@ def _as_frame(a, fmt: int):
     """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
     if fmt == JPGE_FMT_GRAY8:
         a = np.ascontiguousarray(a)  # (the type is checked, not converted: a float plane is no gray frame)
-    elif fmt not in _FMT_420 and fmt not in _FMT_422 and fmt not in _FMT_420P10 and fmt not in _FMT_422P10 and fmt != JPGE_FMT_V210:
+    elif fmt not in _YUV and fmt != JPGE_FMT_V210:
         a = np.ascontiguousarray(a, np.uint8)
     w, h, stride = _frame_geom(a, fmt)
     return np.ascontiguousarray(a, np.uint8), w, h, stride
@@ -855,6 +778,55 @@ def _as_frame(a, fmt: int):
 def _as_frames(frames, fmt: int):
     fr = [_as_frame(f, fmt) for f in frames]
     return [f[0] for f in fr], [f[1:] for f in fr]
+
+
+def _row_pitch(p):
+    """Row pitch in bytes of a torch tensor (rows, ...) whose rows are packed: every dimension
+    after the first at the stride of a contiguous row, unless it has one entry (else ValueError).
+    None for a single row: it has no pitch, so any serves."""
+    run = 1
+    for d in range(p.dim() - 1, 0, -1):
+        if p.stride(d) != run and p.shape[d] > 1:
+            raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride"
+                             + (" and the pairs must be packed" if p.dim() > 2 else ""))
+        run *= p.shape[d]
+    return p.element_size() * p.stride(0) if p.shape[0] > 1 else None
+
+
+def _chroma_offset(planes) -> int:
+    """Bytes from the Y plane to the next of torch planes Y, chroma...: the plane stride."""
+    store = planes[0].untyped_storage().data_ptr()
+    if any(p.untyped_storage().data_ptr() != store for p in planes):
+        raise ValueError("the planes must be views of one allocation")
+    plane_stride = planes[1].data_ptr() - planes[0].data_ptr()
+    if plane_stride <= 0:
+        raise ValueError("the chroma must follow the Y plane in memory")
+    return plane_stride
+
+
+def _plane_geom(L: _Yuv, w: int, h: int, y, c=None, cr=None) -> tuple[int, int]:
+    """(row stride, plane stride) in bytes that say where the torch tensors of a w x h frame in
+    layout L lie: `y` the Y plane or the packed groups, `c` the Cb,Cr pairs or the Cb plane, `cr`
+    the Cr plane.  ValueError where jpge.h's rules cannot express the views: chroma rows at
+    _yuv_chroma_stride of the Y pitch, Cr `chroma rows` rows after Cb."""
+    least = _yuv_least_stride(L, w)
+    stride = _row_pitch(y)
+    if stride is None:
+        stride = least  # (one Y row, hence one row in every plane: no pitch to agree with)
+    if stride < least:
+        raise ValueError(f"rows overlap: pitch {stride}, a row takes {least} bytes")
+    if c is None:
+        return stride, 0
+    plane_stride = _chroma_offset([y, c] + ([] if cr is None else [cr]))
+    cs, rows = _yuv_chroma_stride(L, stride), -(-h // L.vsub)
+    for p in (c, cr):
+        cp = None if p is None else _row_pitch(p)
+        if cp is not None and cp != cs:
+            raise ValueError(f"chroma pitch {cp}: for Y rows at pitch {stride} the layout's " +
+                             ("Cb,Cr rows have the same" if L.order == "semi" else f"Cb and Cr rows have {cs}"))
+    if cr is not None and cr.data_ptr() - c.data_ptr() != cs * rows:
+        raise ValueError(f"the Cr plane must start {cs * rows} bytes ({rows} rows) after the Cb plane")
+    return stride, plane_stride
 
 
 def downscaled_size(w: int, h: int, s: int) -> tuple[int, int]:
@@ -1075,6 +1047,28 @@ class Encoder:
                                       ctypes.byref(n), int(flags)), "encode_rgb8")
         return n.value
 
+    def _encode_view(self, ptr: int, is_cuda: bool, fmt: int, plane_stride: int, w: int, h: int, stride: int,
+                     quality: int, maxval: int, out):
+        """The end of every encode_tensor* method: one frame at `ptr` (device memory if is_cuda) in
+        layout `fmt` through encode_ptr, into a host buffer (-> the .jpg bytes) or into `out`, a
+        uint8 tensor on the device (-> their length); the input layout is put back afterwards."""
+        flags = JPGE_DEVICE_INPUT if is_cuda else 0
+        host_out = None
+        if out is None:
+            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            out_ptr, cap = _p(host_out), host_out.size
+        else:
+            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
+                raise ValueError("out: a contiguous uint8 device tensor")
+            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
+        prev = self.input_format()
+        self.set_input_format(fmt, plane_stride)
+        try:
+            n = self.encode_ptr(ptr, w, h, stride, out_ptr, cap, quality, maxval, flags)
+        finally:
+            self.set_input_format(*prev)
+        return n if host_out is None else host_out[:n].tobytes()
+
     def encode_tensor(self, t, quality: int = 50, out=None, order: str = "rgb", maxval: int = 255, layout=None):
         """One torch uint8 tensor through jpge_encode_rgb8 without a repack: (3, H, W) is the
         planar layout (plane stride t.stride(0)), (H, W, 3) and (H, W, 4) the interleaved ones
@@ -1124,22 +1118,7 @@ class Encoder:
             raise ValueError(f"tensor of shape {shape}: (3, H, W), (H, W, 3), (H, W, 4) or (H, W)")
         if stride < w * input_format_info(fmt)[0] and h > 1:
             raise ValueError("rows overlap")
-        flags = JPGE_DEVICE_INPUT if t.is_cuda else 0
-        host_out = None
-        if out is None:
-            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
-            out_ptr, cap = _p(host_out), host_out.size
-        else:
-            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
-                raise ValueError("out: a contiguous uint8 device tensor")
-            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
-        prev = self.input_format()
-        self.set_input_format(fmt, plane_stride)
-        try:
-            n = self.encode_ptr(t.data_ptr(), w, h, stride, out_ptr, cap, quality, maxval, flags)
-        finally:
-            self.set_input_format(*prev)
-        return n if host_out is None else host_out[:n].tobytes()
+        return self._encode_view(t.data_ptr(), t.is_cuda, fmt, plane_stride, w, h, stride, quality, maxval, out)
 
     def encode_tensor_yuv(self, y, cbcr_or_cb, cr=None, quality: int = 50, out=None):
         """One frame of Y, Cb, Cr torch uint8 tensors (a decoder's surface; full-range BT.601
@@ -1149,9 +1128,7 @@ class Encoder:
         express (jpge.h): unit inner strides, the chroma after the Y plane, NV12's Cb,Cr rows
         at the Y pitch, I420's Cb and Cr rows at pitch (Y pitch + 1) / 2 with Cr ch rows after
         Cb, the 4:4:4 planes at the Y pitch and equally spaced; else ValueError.  A 4:2:0
-        layout needs subsampling mode 420.  Returns the .jpg bytes, or, with `out` a uint8
-        tensor on the frame's device, writes them there and returns their length.  The
-        encoder's input layout is the same afterwards."""
+        layout needs subsampling mode 420.  Result and `out`: as encode_tensor."""
         planes = [y, cbcr_or_cb] + ([] if cr is None else [cr])
         for p in planes:
             if p.element_size() != 1 or p.dtype.is_floating_point or p.device != y.device:
@@ -1170,61 +1147,20 @@ class Encoder:
         else:
             raise ValueError(f"chroma of shape {tuple(c.shape)}" + ("" if cr is None else f", {tuple(cr.shape)}") +
                              f" for a {w}x{h} Y plane: ({ch}, {cw}, 2), two ({ch}, {cw}) or two ({h}, {w})")
-        store = y.untyped_storage().data_ptr()
-        if any(p.untyped_storage().data_ptr() != store for p in planes):
-            raise ValueError("the planes must be views of one allocation")
-        def pitch(p):  # a plane's row pitch (None: one row, any pitch)
-            if p.stride(1) != 1 and p.shape[1] > 1:
-                raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
-            return p.stride(0) if p.shape[0] > 1 else None
-        stride = pitch(y)
-        plane_stride = c.data_ptr() - y.data_ptr()
-        if plane_stride <= 0:
-            raise ValueError("the chroma must follow the Y plane in memory")
-        if fmt == JPGE_FMT_NV12:
-            if c.stride(2) != 1 or (c.stride(1) != 2 and cw > 1):
-                raise ValueError(f"strides {tuple(c.stride())}: Cb,Cr pairs must be packed")
-            cp = c.stride(0) if ch > 1 else None
-            stride = stride if stride is not None else cp if cp is not None else 2 * cw
-            if cp is not None and cp != stride:
-                raise ValueError(f"chroma pitch {cp}: NV12's Cb,Cr rows have the Y pitch {stride}")
-            least = 2 * cw
-        elif fmt == JPGE_FMT_I420:
-            cp, rp = pitch(c), pitch(cr)
-            if stride is None:  # (one Y row: any pitch whose half is the chroma's)
-                stride = 2 * cp if cp is not None else 2 * rp if rp is not None else w
-            cs = (stride + 1) // 2
-            if any(q is not None and q != cs for q in (cp, rp)):
-                raise ValueError(f"chroma pitches {cp}, {rp}: I420's are (Y pitch + 1) / 2 = {cs}")
-            if cr.data_ptr() - c.data_ptr() != cs * ch:
-                raise ValueError(f"the Cr plane must start {cs * ch} bytes ({ch} rows) after the Cb plane")
-            least = w
-        else:
-            cp, rp = pitch(c), pitch(cr)
-            stride = next((q for q in (stride, cp, rp) if q is not None), w)
+        if fmt == JPGE_FMT_YUV444_PLANAR:  # (full-size chroma: not a layout of the table)
+            plane_stride = _chroma_offset(planes)
+            stride, cp, rp = (_row_pitch(p) for p in planes)
+            if stride is None:
+                stride = w  # (one row in every plane: any pitch)
             if any(q is not None and q != stride for q in (cp, rp)):
                 raise ValueError(f"chroma pitches {cp}, {rp}: the planes share the Y pitch {stride}")
             if cr.data_ptr() - c.data_ptr() != plane_stride:
                 raise ValueError("the Y, Cb and Cr planes must be equally spaced")
-            least = w
-        if stride < least:
-            raise ValueError("rows overlap")
-        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
-        host_out = None
-        if out is None:
-            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
-            out_ptr, cap = _p(host_out), host_out.size
+            if stride < w:
+                raise ValueError("rows overlap")
         else:
-            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
-                raise ValueError("out: a contiguous uint8 device tensor")
-            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
-        prev = self.input_format()
-        self.set_input_format(fmt, plane_stride)
-        try:
-            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
-        finally:
-            self.set_input_format(*prev)
-        return n if host_out is None else host_out[:n].tobytes()
+            stride, plane_stride = _plane_geom(_YUV[fmt], w, h, y, c, cr)
+        return self._encode_view(y.data_ptr(), y.is_cuda, fmt, plane_stride, w, h, stride, quality, 255, out)
 
     def encode_tensor_yuv10(self, y, cbcr_or_cb, cr=None, quality: int = 50, out=None):
         """One 10-bit 4:2:0 frame of 2-D 16-bit torch tensors (a Main10 decoder's surface), read in
@@ -1234,9 +1170,7 @@ class Encoder:
         on one device, at offsets the layout can express (jpge.h): unit inner strides, the chroma
         after the Y plane, P010's Cb,Cr rows at the Y pitch, I010's Cb and Cr rows at pitch
         2 * ceil(Y pitch in bytes / 4) with Cr ch rows after Cb; else ValueError.  Needs
-        subsampling mode 420.  Returns the .jpg bytes, or, with `out` a uint8 tensor on the
-        frame's device, writes them there and returns their length.  The encoder's input layout
-        is the same afterwards."""
+        subsampling mode 420.  Result and `out`: as encode_tensor."""
         planes = [y, cbcr_or_cb] + ([] if cr is None else [cr])
         for p in planes:
             if p.element_size() != 2 or p.dtype.is_floating_point or p.dim() != 2 or p.device != y.device:
@@ -1253,51 +1187,8 @@ class Encoder:
         else:
             raise ValueError(f"chroma of shape {tuple(c.shape)}" + ("" if cr is None else f", {tuple(cr.shape)}") +
                              f" for a {w}x{h} Y plane: ({ch}, {2 * cw}) or two ({ch}, {cw})")
-        store = y.untyped_storage().data_ptr()
-        if any(p.untyped_storage().data_ptr() != store for p in planes):
-            raise ValueError("the planes must be views of one allocation")
-        def pitch(p):  # a plane's row pitch in bytes (None: one row, any pitch)
-            if p.stride(1) != 1 and p.shape[1] > 1:
-                raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
-            return 2 * p.stride(0) if p.shape[0] > 1 else None
-        stride = pitch(y)
-        plane_stride = c.data_ptr() - y.data_ptr()
-        if plane_stride <= 0:
-            raise ValueError("the chroma must follow the Y plane in memory")
-        if fmt == JPGE_FMT_P010:
-            cp = pitch(c)
-            stride = stride if stride is not None else cp if cp is not None else 4 * cw
-            if cp is not None and cp != stride:
-                raise ValueError(f"chroma pitch {cp}: P010's Cb,Cr rows have the Y pitch {stride}")
-            least = 4 * cw
-        else:
-            cp, rp = pitch(c), pitch(cr)
-            if stride is None:  # (one Y row: any pitch whose half is the chroma's)
-                stride = 2 * cp if cp is not None else 2 * rp if rp is not None else 2 * w
-            cs = 2 * ((stride + 3) // 4)
-            if any(q is not None and q != cs for q in (cp, rp)):
-                raise ValueError(f"chroma pitches {cp}, {rp}: I010's are 2 * ceil(Y pitch / 4) = {cs}")
-            if cr.data_ptr() - c.data_ptr() != cs * ch:
-                raise ValueError(f"the Cr plane must start {cs * ch} bytes ({ch} rows) after the Cb plane")
-            least = 2 * w
-        if stride < least:
-            raise ValueError("rows overlap")
-        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
-        host_out = None
-        if out is None:
-            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
-            out_ptr, cap = _p(host_out), host_out.size
-        else:
-            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
-                raise ValueError("out: a contiguous uint8 device tensor")
-            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
-        prev = self.input_format()
-        self.set_input_format(fmt, plane_stride)
-        try:
-            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
-        finally:
-            self.set_input_format(*prev)
-        return n if host_out is None else host_out[:n].tobytes()
+        stride, plane_stride = _plane_geom(_YUV[fmt], w, h, y, c, cr)
+        return self._encode_view(y.data_ptr(), y.is_cuda, fmt, plane_stride, w, h, stride, quality, 255, out)
 
     def encode_tensor_yuv422p10(self, y_or_packed, cbcr_or_cb=None, cr=None, quality: int = 50, out=None):
         """One 10-bit 4:2:2 frame of 2-D 16-bit torch tensors (an SDI capture buffer, or a ProRes /
@@ -1309,85 +1200,31 @@ class Encoder:
         layout can express (jpge.h): unit inner strides, the chroma after the Y plane, P210's
         Cb,Cr rows at the Y pitch, I210's Cb and Cr rows at pitch 2 * ceil(Y pitch in bytes / 4)
         with Cr H rows after Cb; else ValueError.  Every subsampling mode takes these layouts (422
-        is the native one).  Returns the .jpg bytes, or, with `out` a uint8 tensor on the frame's
-        device, writes them there and returns their length.  The encoder's input layout is the
-        same afterwards."""
-        y = y_or_packed
-        planes = [p for p in (y, cbcr_or_cb, cr) if p is not None]
+        is the native one).  Result and `out`: as encode_tensor."""
+        y, c = y_or_packed, cbcr_or_cb
+        planes = [p for p in (y, c, cr) if p is not None]
         for p in planes:
             if p.element_size() != 2 or p.dtype.is_floating_point or p.dim() != 2 or p.device != y.device:
                 raise ValueError("encode_tensor_yuv422p10 takes 2-D 16-bit integer tensors on one device")
         if y.numel() == 0:
             raise ValueError(f"Y plane of shape {tuple(y.shape)}: (H, W)")
-        if cbcr_or_cb is None and cr is not None:
+        if c is None and cr is not None:
             raise ValueError("a Cr plane goes with a Cb plane")
-        def pitch(p):  # a plane's row pitch in bytes (None: one row, any pitch)
-            if p.stride(1) != 1 and p.shape[1] > 1:
-                raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
-            return 2 * p.stride(0) if p.shape[0] > 1 else None
-        h = int(y.shape[0])
-        plane_stride = 0
-        if cbcr_or_cb is None:  # packed
-            if y.shape[1] % 4:
+        h, w = y.shape
+        cw = (w + 1) // 2
+        if c is None:  # packed
+            if w % 4:
                 raise ValueError(f"packed frame of shape {tuple(y.shape)}: (H, 4 * cw), whole groups of four words")
-            cw = int(y.shape[1]) // 4
-            w = 2 * cw
-            fmt = JPGE_FMT_Y210
-            stride = pitch(y)
-            stride = stride if stride is not None else 8 * cw
-            least = 8 * cw
+            w, fmt = w // 2, JPGE_FMT_Y210
+        elif cr is None and tuple(c.shape) == (h, 2 * cw):
+            fmt = JPGE_FMT_P210
+        elif cr is not None and tuple(c.shape) == (h, cw) == tuple(cr.shape):
+            fmt = JPGE_FMT_I210
         else:
-            w = int(y.shape[1])
-            cw = (w + 1) // 2
-            c = cbcr_or_cb
-            if cr is None and tuple(c.shape) == (h, 2 * cw):
-                fmt = JPGE_FMT_P210
-            elif cr is not None and tuple(c.shape) == (h, cw) == tuple(cr.shape):
-                fmt = JPGE_FMT_I210
-            else:
-                raise ValueError(f"chroma of shapes {[tuple(p.shape) for p in planes[1:]]} for a {w}x{h} Y plane: "
-                                 f"({h}, {2 * cw}) or two ({h}, {cw})")
-            store = y.untyped_storage().data_ptr()
-            if any(p.untyped_storage().data_ptr() != store for p in planes):
-                raise ValueError("the planes must be views of one allocation")
-            stride = pitch(y)
-            plane_stride = c.data_ptr() - y.data_ptr()
-            if plane_stride <= 0:
-                raise ValueError("the chroma must follow the Y plane in memory")
-            if fmt == JPGE_FMT_P210:
-                cp = pitch(c)
-                stride = stride if stride is not None else 4 * cw
-                if cp is not None and cp != stride:
-                    raise ValueError(f"chroma pitch {cp}: P210's Cb,Cr rows have the Y pitch {stride}")
-                least = 4 * cw
-            else:
-                cp, rp = pitch(c), pitch(cr)
-                if stride is None:
-                    stride = 2 * w
-                cs = 2 * ((stride + 3) // 4)
-                if any(q is not None and q != cs for q in (cp, rp)):
-                    raise ValueError(f"chroma pitches {cp}, {rp}: I210's are 2 * ceil(Y pitch / 4) = {cs}")
-                if cr.data_ptr() - c.data_ptr() != cs * h:
-                    raise ValueError(f"the Cr plane must start {cs * h} bytes ({h} rows) after the Cb plane")
-                least = 2 * w
-        if stride < least:
-            raise ValueError("rows overlap")
-        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
-        host_out = None
-        if out is None:
-            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
-            out_ptr, cap = _p(host_out), host_out.size
-        else:
-            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
-                raise ValueError("out: a contiguous uint8 device tensor")
-            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
-        prev = self.input_format()
-        self.set_input_format(fmt, plane_stride)
-        try:
-            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
-        finally:
-            self.set_input_format(*prev)
-        return n if host_out is None else host_out[:n].tobytes()
+            raise ValueError(f"chroma of shapes {[tuple(p.shape) for p in planes[1:]]} for a {w}x{h} Y plane: "
+                             f"({h}, {2 * cw}) or two ({h}, {cw})")
+        stride, plane_stride = _plane_geom(_YUV[fmt], w, h, y, c, cr)
+        return self._encode_view(y.data_ptr(), y.is_cuda, fmt, plane_stride, w, h, stride, quality, 255, out)
 
     def encode_tensor_v210(self, t, width: int, quality: int = 50, out=None):
         """One v210 frame (JPGE_FMT_V210: a 10-bit SDI capture buffer) of a 2-D device or host torch
@@ -1396,8 +1233,7 @@ class Encoder:
         for what the library would refuse: another type or rank, an inner stride other than 1, a row
         shorter than v210_row_bytes(width), a base or row pitch that is no multiple of 4, a width
         outside 1..65535.  Every subsampling mode takes the layout (422 is the native one).
-        Returns the .jpg bytes, or, with `out` a uint8 tensor on the frame's device, writes them
-        there and returns their length.  The encoder's input layout is the same afterwards."""
+        Result and `out`: as encode_tensor."""
         import torch
         if t.dtype not in (torch.uint8, torch.int32) or t.dim() != 2 or t.numel() == 0:
             raise ValueError("encode_tensor_v210 takes a 2-D uint8 or int32 tensor of rows")
@@ -1414,22 +1250,7 @@ class Encoder:
             raise ValueError("rows overlap")
         if stride % 4 or t.data_ptr() % 4:
             raise ValueError("the base and the row pitch must be multiples of 4")
-        flags = JPGE_DEVICE_INPUT if t.is_cuda else 0
-        host_out = None
-        if out is None:
-            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
-            out_ptr, cap = _p(host_out), host_out.size
-        else:
-            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
-                raise ValueError("out: a contiguous uint8 device tensor")
-            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
-        prev = self.input_format()
-        self.set_input_format(JPGE_FMT_V210, 0)
-        try:
-            n = self.encode_ptr(t.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
-        finally:
-            self.set_input_format(*prev)
-        return n if host_out is None else host_out[:n].tobytes()
+        return self._encode_view(t.data_ptr(), t.is_cuda, JPGE_FMT_V210, 0, w, h, stride, quality, 255, out)
 
     def encode_tensor_yuv422(self, y_or_packed, cbcr_or_cb=None, cr=None, quality: int = 50, out=None,
                              layout=None):
@@ -1442,38 +1263,30 @@ class Encoder:
         device, at offsets the layout can express (jpge.h): unit inner strides, the chroma
         after the Y plane, NV16's Cb,Cr rows at the Y pitch, I422's Cb and Cr rows at pitch
         (Y pitch + 1) / 2 with Cr H rows after Cb; else ValueError.  Every subsampling mode
-        takes these layouts (422 is the native one).  Returns the .jpg bytes, or, with `out` a
-        uint8 tensor on the frame's device, writes them there and returns their length.  The
-        encoder's input layout is the same afterwards."""
-        y = y_or_packed
-        planes = [p for p in (y, cbcr_or_cb, cr) if p is not None]
+        takes these layouts (422 is the native one).  Result and `out`: as encode_tensor."""
+        y, c = y_or_packed, cbcr_or_cb
+        planes = [p for p in (y, c, cr) if p is not None]
         for p in planes:
             if p.element_size() != 1 or p.dtype.is_floating_point or p.device != y.device:
                 raise ValueError("encode_tensor_yuv422 takes uint8 tensors on one device")
-        plane_stride = 0
         if y.dim() == 3:  # packed
             if layout not in ("yuyv", "uyvy"):
                 raise ValueError(f"layout {layout!r}: a packed (H, W, 2) tensor is 'yuyv' or 'uyvy'")
-            if cbcr_or_cb is not None or cr is not None:
+            if c is not None or cr is not None:
                 raise ValueError("a packed frame is one tensor")
             if y.shape[2] != 2 or y.numel() == 0:
                 raise ValueError(f"packed frame of shape {tuple(y.shape)}: (H, W, 2)")
-            h, w = int(y.shape[0]), int(y.shape[1])
+            h, w = y.shape[:2]
             if w % 2:
                 raise ValueError(f"packed frame of odd width {w}: a (H, W, 2) tensor cannot hold the last group")
-            if y.stride(2) != 1 or y.stride(1) != 2:
-                raise ValueError(f"strides {tuple(y.stride())}: the inner dimensions must be packed")
-            stride = y.stride(0) if h > 1 else 2 * w
-            least = 2 * w
             fmt = JPGE_FMT_YUYV if layout == "yuyv" else JPGE_FMT_UYVY
         else:
             if layout is not None:
                 raise ValueError("layout goes with a packed (H, W, 2) tensor")
             if y.dim() != 2 or y.numel() == 0:
                 raise ValueError(f"Y plane of shape {tuple(y.shape)}: (H, W)")
-            h, w = int(y.shape[0]), int(y.shape[1])
+            h, w = y.shape
             cw = (w + 1) // 2
-            c = cbcr_or_cb
             if c is not None and cr is None and tuple(c.shape) == (h, cw, 2):
                 fmt = JPGE_FMT_NV16
             elif c is not None and cr is not None and tuple(c.shape) == (h, cw) == tuple(cr.shape):
@@ -1481,53 +1294,8 @@ class Encoder:
             else:
                 raise ValueError(f"chroma of shapes {[tuple(p.shape) for p in planes[1:]]} for a {w}x{h} Y plane: "
                                  f"({h}, {cw}, 2) or two ({h}, {cw})")
-            store = y.untyped_storage().data_ptr()
-            if any(p.untyped_storage().data_ptr() != store for p in planes):
-                raise ValueError("the planes must be views of one allocation")
-            def pitch(p):  # a plane's row pitch (None: one row, any pitch)
-                if p.stride(1) != 1 and p.shape[1] > 1:
-                    raise ValueError(f"strides {tuple(p.stride())}: the inner dimension must have unit stride")
-                return p.stride(0) if p.shape[0] > 1 else None
-            stride = pitch(y)
-            plane_stride = c.data_ptr() - y.data_ptr()
-            if plane_stride <= 0:
-                raise ValueError("the chroma must follow the Y plane in memory")
-            if fmt == JPGE_FMT_NV16:
-                if c.stride(2) != 1 or (c.stride(1) != 2 and cw > 1):
-                    raise ValueError(f"strides {tuple(c.stride())}: Cb,Cr pairs must be packed")
-                cp = c.stride(0) if h > 1 else None
-                stride = stride if stride is not None else 2 * cw
-                if cp is not None and cp != stride:
-                    raise ValueError(f"chroma pitch {cp}: NV16's Cb,Cr rows have the Y pitch {stride}")
-                least = 2 * cw
-            else:
-                cp, rp = pitch(c), pitch(cr)
-                if stride is None:
-                    stride = w
-                cs = (stride + 1) // 2
-                if any(q is not None and q != cs for q in (cp, rp)):
-                    raise ValueError(f"chroma pitches {cp}, {rp}: I422's are (Y pitch + 1) / 2 = {cs}")
-                if cr.data_ptr() - c.data_ptr() != cs * h:
-                    raise ValueError(f"the Cr plane must start {cs * h} bytes ({h} rows) after the Cb plane")
-                least = w
-        if stride < least:
-            raise ValueError("rows overlap")
-        flags = JPGE_DEVICE_INPUT if y.is_cuda else 0
-        host_out = None
-        if out is None:
-            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
-            out_ptr, cap = _p(host_out), host_out.size
-        else:
-            if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
-                raise ValueError("out: a contiguous uint8 device tensor")
-            out_ptr, cap, flags = out.data_ptr(), out.numel(), flags | JPGE_DEVICE_OUTPUT
-        prev = self.input_format()
-        self.set_input_format(fmt, plane_stride)
-        try:
-            n = self.encode_ptr(y.data_ptr(), w, h, stride, out_ptr, cap, quality, 255, flags)
-        finally:
-            self.set_input_format(*prev)
-        return n if host_out is None else host_out[:n].tobytes()
+        stride, plane_stride = _plane_geom(_YUV[fmt], w, h, y, c, cr)
+        return self._encode_view(y.data_ptr(), y.is_cuda, fmt, plane_stride, w, h, stride, quality, 255, out)
 
     def encode_batch_dev(self, frames: list[tuple[int, int, int, int]], outs: list[tuple[int, int]],
                          quality: int = 50, maxval: int = 255,

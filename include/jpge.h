@@ -440,6 +440,72 @@ int jpge_downscaled_size(uint32_t width, uint32_t height, int factor, uint32_t* 
 int jpge_downscale_frame(int format, const uint8_t* src, uint32_t width, uint32_t height, size_t stride,
                          size_t plane_stride, int factor, uint8_t* dst, size_t dst_stride, size_t dst_plane_stride);
 
+/* ---- Orientation of the input (an addition; replaces nothing in the reference) ----
+ * A frame whose rows are not the picture's rows (a sensor mounted sideways, portrait video,
+ * a mirrored front camera) is coded flipped, rotated or transposed: the transform kernel
+ * reads the source in the turned order while it stages a tile, so no transpose or flip pass
+ * runs and no second surface exists.  The stream stays plain JFIF, without an orientation
+ * tag: the pixels are turned.  The values name the operation applied to the pixels.  With the
+ * source S of Ws x Hs pixels, S(r, c) its pixel at row r, column c, the coded frame O is
+ * ow x oh:
+ *
+ *   value  name                       ow x oh   O(y, x) =              numpy
+ *   0      JPGE_ORIENT_NONE (default) Ws x Hs   S(y, x)                a
+ *   1      JPGE_ORIENT_FLIP_H         Ws x Hs   S(y, Ws-1-x)           a[:, ::-1]
+ *   2      JPGE_ORIENT_ROT180         Ws x Hs   S(Hs-1-y, Ws-1-x)      a[::-1, ::-1]
+ *   3      JPGE_ORIENT_FLIP_V         Ws x Hs   S(Hs-1-y, x)           a[::-1]
+ *   4      JPGE_ORIENT_TRANSPOSE      Hs x Ws   S(x, y)                a.transpose(1, 0, 2)
+ *   5      JPGE_ORIENT_ROT90          Hs x Ws   S(Hs-1-x, y)           np.rot90(a, -1)   (clockwise)
+ *   6      JPGE_ORIENT_TRANSVERSE     Hs x Ws   S(Hs-1-x, Ws-1-y)      np.rot90(a, 2).transpose(1, 0, 2)
+ *   7      JPGE_ORIENT_ROT270         Hs x Ws   S(x, Ws-1-y)           np.rot90(a, 1)    (counter-clockwise)
+ *
+ * The .jpg of a frame coded with orientation o is, byte for byte, the .jpg of O
+ * (jpge_orient_frame) coded with JPGE_ORIENT_NONE in the same layout, under every other
+ * setting: quality tables, maxval, subsampling mode, restart interval, Huffman mode, frame
+ * sets and lanes.  SOF0 carries ow x oh; the padding to whole MCUs replicates O's right and
+ * bottom edge (the kernel clamps in O's coordinates first and maps to the source second);
+ * alpha is ignored.
+ *
+ * The setting applies to the calls jpge_set_downscale applies to: jpge_encode_rgb8,
+ * jpge_encode_batch, jpge_encode_file(s), jpge_fdct_quant and jpge_symbol_stats (the last two
+ * return O's planes and histograms), and on a group member's context jpge_group_encode_batch.
+ * Layouts with o != 0: JPGE_FMT_RGB8, _BGR8, _RGBA8, _BGRA8.  Orientations 1-3 in every
+ * subsampling mode; 4-7 in the three modes with 16x16 MCUs (JPGE_S420_M, JPGE_S420,
+ * JPGE_S420_LM).  Everything else with o != 0 returns JPGE_E_ARG (a batch: the frame's status)
+ * before anything is queued: any other layout, 4-7 in JPGE_S444 / _S422 / _S411, a downscale
+ * factor above 1 together with o != 0, jpge_stripe_transform and jpge_group_encode_striped.
+ * jpge_encode_planes and the plane stages ignore the setting.  The limits on width, height and
+ * stride, and the 32-bit offset check, are the source's; jpge_max_jpeg_bytes(ow, oh) bounds the
+ * output.
+ *
+ * Speed: the fast path needs base and stride 16-byte aligned, as without an orientation.  The
+ * mirrored orientations (1, 2, 6, 7) read each row's runs from its far end, so they need in
+ * addition a row of a multiple of 16 bytes: Ws % 16 == 0 for 3-byte pixels, Ws % 4 == 0 for
+ * 4-byte pixels.  A mirrored frame whose width misses that is read pixel by pixel on every
+ * tile: correct, at about twice the transform kernel's time.
+ *
+ * 0..7; anything else, or a NULL context: JPGE_E_ARG, the setting unchanged. */
+#define JPGE_ORIENT_NONE 0
+#define JPGE_ORIENT_FLIP_H 1
+#define JPGE_ORIENT_ROT180 2
+#define JPGE_ORIENT_FLIP_V 3
+#define JPGE_ORIENT_TRANSPOSE 4
+#define JPGE_ORIENT_ROT90 5
+#define JPGE_ORIENT_TRANSVERSE 6
+#define JPGE_ORIENT_ROT270 7
+int jpge_set_orientation(jpge_ctx* ctx, int orientation);
+int jpge_get_orientation(jpge_ctx* ctx, int* orientation);
+/* ow, oh of a width x height frame; host only.  JPGE_E_ARG: a value outside 0..7, a zero
+ * dimension or a NULL pointer. */
+int jpge_oriented_size(uint32_t width, uint32_t height, int orientation, uint32_t* ow, uint32_t* oh);
+/* The table above in plain C++, host only: src (width x height in `format`, row pitch stride,
+ * 0 = dense) to dst (ow x oh in the same layout, dst_stride likewise; src and dst must not
+ * overlap).  A 4-byte layout's fourth byte is copied.  Bytes of dst outside its rows' pixels
+ * are not written.  JPGE_E_ARG: a layout other than the four above, a value outside 0..7, a
+ * zero dimension, a NULL pointer or a stride below a row's bytes. */
+int jpge_orient_frame(int format, const uint8_t* src, uint32_t width, uint32_t height, size_t stride, int orientation,
+                      uint8_t* dst, size_t dst_stride);
+
 /* Worst-case .jpg size for a frame, in any subsampling mode (header + 2x
  * worst-case entropy + RST markers + EOI). */
 size_t jpge_max_jpeg_bytes(uint32_t width, uint32_t height);

@@ -41,6 +41,9 @@ JPGE_FMT_Y210, JPGE_FMT_P210, JPGE_FMT_I210 = 40, 41, 42
 #: v210 (10-bit SDI capture; QuickTime / AVI "uncompressed 10-bit"): the same samples, three to a
 #: 32-bit word, six pixels in 16 bytes; host frames from pack_v210
 JPGE_FMT_V210 = 48
+# orientations (jpge.h JPGE_ORIENT_*): the operation applied to the pixels
+JPGE_ORIENT_NONE, JPGE_ORIENT_FLIP_H, JPGE_ORIENT_ROT180, JPGE_ORIENT_FLIP_V = 0, 1, 2, 3
+JPGE_ORIENT_TRANSPOSE, JPGE_ORIENT_ROT90, JPGE_ORIENT_TRANSVERSE, JPGE_ORIENT_ROT270 = 4, 5, 6, 7
 #: 4:2:2 frames of the same samples (one Cb, Cr per horizontal pixel pair of every row): packed
 #: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 groups, NV16 (Y plane + Cb,Cr rows), I422 (three planes); host
 #: frames from pack_yuv422
@@ -76,6 +79,7 @@ EXPORTS = (
     "jpge_set_huffman", "jpge_get_huffman", "jpge_standard_huffman",
     "jpge_set_yuv_transform", "jpge_get_yuv_transform", "jpge_yuv_preset",
     "jpge_set_downscale", "jpge_get_downscale", "jpge_downscaled_size", "jpge_downscale_frame",
+    "jpge_set_orientation", "jpge_get_orientation", "jpge_oriented_size", "jpge_orient_frame",
     "jpge_max_jpeg_bytes", "jpge_quality_tables", "jpge_encode_rgb8", "jpge_encode_batch",
     "jpge_fdct_quant", "jpge_symbol_stats", "jpge_huffman_table", "jpge_huffman_text", "jpge_parse_ppm",
     "jpge_ppm_info", "jpge_encode_file", "jpge_encode_files", "jpge_synth_rgb8", "jpge_arai_constants",
@@ -226,6 +230,10 @@ def lib() -> ctypes.CDLL:
         L.jpge_get_downscale.argtypes = [vp, ctypes.POINTER(i32)]
         L.jpge_downscaled_size.argtypes = [u32, u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
         L.jpge_downscale_frame.argtypes = [i32, vp, u32, u32, sz, sz, i32, vp, sz, sz]
+        L.jpge_set_orientation.argtypes = [vp, i32]
+        L.jpge_get_orientation.argtypes = [vp, ctypes.POINTER(i32)]
+        L.jpge_oriented_size.argtypes = [u32, u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.jpge_orient_frame.argtypes = [i32, vp, u32, u32, sz, i32, vp, sz]
         L.jpge_device_count.argtypes = [ctypes.POINTER(i32)]
         L.jpge_max_jpeg_bytes.restype = sz
         L.jpge_max_jpeg_bytes.argtypes = [u32, u32]
@@ -857,6 +865,26 @@ def downscale_frame(a, fmt: int, s: int):
     return out
 
 
+def oriented_size(w: int, h: int, o: int) -> tuple[int, int]:
+    """(ow, oh) of a w x h frame under orientation o (JPGE_ORIENT_*): (h, w) for the transposed
+    ones, 4-7 (jpge_oriented_size)."""
+    ow, oh = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().jpge_oriented_size(int(w), int(h), int(o), ctypes.byref(ow), ctypes.byref(oh)), "oriented_size")
+    return ow.value, oh.value
+
+
+def orient_frame(a, fmt: int, o: int):
+    """The frame an encode with Encoder.set_orientation(o) codes (jpge_orient_frame, on the
+    host): `a`, (H, W, C) in layout `fmt` (RGB8, BGR8, RGBA8, BGRA8) -> the (oh, ow, C) frame
+    in the same layout; a fourth byte is copied."""
+    a, w, h, stride = _as_frame(a, fmt)
+    ow, oh = oriented_size(w, h, o)
+    bpp = input_format_info(fmt)[0]
+    out = np.zeros((oh, ow, bpp), np.uint8)
+    _check(lib().jpge_orient_frame(int(fmt), _p(a), w, h, stride, int(o), _p(out), ow * bpp), "orient_frame")
+    return out
+
+
 def device_count() -> int:
     n = ctypes.c_int(0)
     lib().jpge_device_count(ctypes.byref(n))
@@ -885,6 +913,8 @@ def _close_live_encoders() -> None:
 class Encoder:
     """One GPU context (jpge_open).  Host-array methods copy in/out; the `*_dev`
     variants take device pointers (ints) for HBM-resident frames."""
+
+    _orient = JPGE_ORIENT_NONE  # the orientation as set through this object (sizes the output buffers)
 
     def __init__(self, device: int = 0, lanes: int = 0):
         """lanes: concurrent pipelines on the device (0 = JPGE_LANES or the default 4)."""
@@ -1008,6 +1038,26 @@ class Encoder:
         _check(lib().jpge_get_downscale(self._ctx, ctypes.byref(f)), "get_downscale")
         return f.value
 
+    def set_orientation(self, o: int) -> None:
+        """Orientation of the following encodes (the calls set_downscale applies to): one of
+        JPGE_ORIENT_*, named by the operation applied to the pixels.  A W x H frame is coded
+        flipped, rotated or transposed (4-7: as H x W), turned inside the transform kernel: the
+        bytes are those of encoding orient_frame(frame, fmt, o).  RGB8, BGR8, RGBA8 and BGRA8
+        input; 4-7 in the 16x16-MCU subsampling modes; other layouts, a downscale factor above
+        1 and the stripe phases fail with JPGE_E_ARG while it is set."""
+        _check(lib().jpge_set_orientation(self._ctx, int(o)), "set_orientation")
+        self._orient = int(o)
+
+    @property
+    def orientation(self) -> int:
+        o = ctypes.c_int32()
+        _check(lib().jpge_get_orientation(self._ctx, ctypes.byref(o)), "get_orientation")
+        return o.value
+
+    def _cap(self, w: int, h: int) -> int:
+        # the output bound of a w x h source: the coded frame's (oriented_size)
+        return max_jpeg_bytes(h, w) if self._orient >= JPGE_ORIENT_TRANSPOSE else max_jpeg_bytes(w, h)
+
     def lanes(self) -> int:
         n = ctypes.c_int32()
         _check(lib().jpge_get_lanes(self._ctx, ctypes.byref(n)), "get_lanes")
@@ -1028,7 +1078,7 @@ class Encoder:
         (the frame shaped for the input layout, set_input_format)."""
         rgb, w, h, stride = _as_frame(rgb, self._fmt)
         qy, qc = self._tables(quality, qy, self._gray_qc(qy, qc))
-        out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+        out = np.empty(self._cap(w, h), np.uint8)
         n = ctypes.c_size_t()
         _check(lib().jpge_encode_rgb8(self._ctx, _p(rgb), w, h, stride, int(maxval), _p(qy), _p(qc), _p(out),
                                       out.size, ctypes.byref(n), 0), "encode")
@@ -1055,7 +1105,7 @@ class Encoder:
         flags = JPGE_DEVICE_INPUT if is_cuda else 0
         host_out = None
         if out is None:
-            host_out = np.empty(max_jpeg_bytes(w, h), np.uint8)
+            host_out = np.empty(self._cap(w, h), np.uint8)
             out_ptr, cap = _p(host_out), host_out.size
         else:
             if not out.is_cuda or not out.is_contiguous() or out.element_size() != 1:
@@ -1328,7 +1378,7 @@ class Encoder:
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         qy, qc = self._tables(quality, None, None)
         frames, geom = _as_frames(frames, self._fmt)
-        outs = [np.empty(max_jpeg_bytes(w, h), np.uint8) for w, h, _ in geom]
+        outs = [np.empty(self._cap(w, h), np.uint8) for w, h, _ in geom]
         arr = (Frame * len(frames))()
         for i, (f, o, (w, h, stride)) in enumerate(zip(frames, outs, geom)):
             arr[i].rgb, arr[i].width, arr[i].height = _p(f), w, h
@@ -1349,6 +1399,7 @@ class Encoder:
             return y, None, None
         yh, yv = SUBSAMPLING[getattr(self, "_sub", 420)]
         dw, dh = downscaled_size(w, h, self.downscale)  # (the coded frame's blocks)
+        dw, dh = oriented_size(dw, dh, self.orientation)
         mw, mh = -(-dw // (8 * yh)), -(-dh // (8 * yv))  # MCUs across / down
         y = np.zeros((mw * yh * mh * yv, 64), np.int16)
         cb = np.zeros((mw * mh, 64), np.int16)
@@ -1472,6 +1523,8 @@ class Group:
     """A device group (jpge_group_open): one process, one context per listed device,
     RCCL over xGMI between distinct devices (a device listed twice: host exchanges)."""
 
+    _orient = JPGE_ORIENT_NONE  # the orientation as set through this object (sizes the output buffers)
+
     def __init__(self, devices, lanes: int = 0):
         devs = (ctypes.c_int * len(devices))(*devices)
         self._g = ctypes.c_void_p()
@@ -1533,11 +1586,22 @@ class Group:
             _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
             _check(lib().jpge_set_downscale(c, int(factor)), "set_downscale")
 
+    def set_orientation(self, o: int) -> None:
+        """Orientation of every member's context (Encoder.set_orientation): for encode_batch;
+        encode_striped needs JPGE_ORIENT_NONE."""
+        for m in range(self.size()[0]):
+            c = ctypes.c_void_p()
+            _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
+            _check(lib().jpge_set_orientation(c, int(o)), "set_orientation")
+        self._orient = int(o)
+
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         """Config 4: frame i on member i mod N."""
         qy, qc = quality_tables(quality)
         frames, geom = _as_frames(frames, self._fmt)
-        outs = [np.empty(max_jpeg_bytes(w, h), np.uint8) for w, h, _ in geom]
+        # (the coded frame's bound: a transposed orientation swaps the sides)
+        t = self._orient >= JPGE_ORIENT_TRANSPOSE
+        outs = [np.empty(max_jpeg_bytes(h, w) if t else max_jpeg_bytes(w, h), np.uint8) for w, h, _ in geom]
         arr = (Frame * len(frames))()
         for i, (f, o, (w, h, stride)) in enumerate(zip(frames, outs, geom)):
             arr[i].rgb, arr[i].width, arr[i].height = _p(f), w, h

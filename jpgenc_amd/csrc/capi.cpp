@@ -392,6 +392,43 @@ int jpge_downscale_frame(int format, const uint8_t* src, uint32_t w, uint32_t h,
     return JPGE_OK;
 }
 
+int jpge_set_orientation(jpge_ctx* ctx, int o) {
+    CtxUse use(ctx);
+    if (!use) return JPGE_E_ARG;
+    return ctx->enc->set_orientation(o) ? JPGE_E_ARG : JPGE_OK;
+}
+
+int jpge_get_orientation(jpge_ctx* ctx, int* o) {
+    CtxUse use(ctx);
+    if (!use || !o) return JPGE_E_ARG;
+    *o = ctx->enc->orientation();
+    return JPGE_OK;
+}
+
+int jpge_oriented_size(uint32_t w, uint32_t h, int o, uint32_t* ow, uint32_t* oh) {
+    if (!jpge::orient_valid(o) || !w || !h || !ow || !oh) return JPGE_E_ARG;
+    *ow = jpge::orient_w(w, h, o);
+    *oh = jpge::orient_h(w, h, o);
+    return JPGE_OK;
+}
+
+int jpge_orient_frame(int format, const uint8_t* src, uint32_t w, uint32_t h, size_t stride, int o, uint8_t* dst,
+                      size_t dst_stride) {
+    if (!jpge::orient_valid(o) || !jpge::orient_fmt(format) || !src || !dst || !w || !h) return JPGE_E_ARG;
+    const uint32_t ow = jpge::orient_w(w, h, o), oh = jpge::orient_h(w, h, o);
+    const size_t bpp = jpge::fmt_bpp(format), row = bpp * w, drow = bpp * ow;
+    if (!stride) stride = row;
+    if (!dst_stride) dst_stride = drow;
+    if (stride < row || dst_stride < drow) return JPGE_E_ARG;
+    for (uint32_t y = 0; y < oh; ++y)
+        for (uint32_t x = 0; x < ow; ++x) {
+            uint32_t sr, sc;
+            jpge::orient_src(o, w, h, y, x, sr, sc);
+            std::memcpy(dst + (size_t)y * dst_stride + (size_t)x * bpp, src + (size_t)sr * stride + (size_t)sc * bpp, bpp);
+        }
+    return JPGE_OK;
+}
+
 int jpge_input_format_info(int format, int* bytes_per_pixel, int* planes) {
     if (!jpge::fmt_valid(format)) return JPGE_E_ARG;
     if (bytes_per_pixel) *bytes_per_pixel = (int)jpge::fmt_bpp(format);
@@ -592,7 +629,9 @@ int jpge_encode_file(jpge_ctx* ctx, const char* ppm_path, const char* jpg_path, 
     uint8_t qy[64], qc[64];
     if (quality < 1 || quality > 100) return JPGE_E_ARG;
     jpge::quality_tables(quality, qy, qc);
-    std::vector<uint8_t> out(jpge::Encoder::max_jpeg_bytes(img.width, img.height));
+    // (either way up: the context's orientation may transpose the frame)
+    std::vector<uint8_t> out(std::max(jpge::Encoder::max_jpeg_bytes(img.width, img.height),
+                                      jpge::Encoder::max_jpeg_bytes(img.height, img.width)));
     size_t len = 0;
     st = encode_pixels(ctx, img.rgb.data(), img.width, img.height, 0, img.maxval, qy, qc, out.data(), out.size(),
                        &len, 0, false);

@@ -11,7 +11,11 @@
 //                                  (jpge_set_huffman; not with --gpus / --devices);
 //   --downscale 2|4                code the image at 1/2 or 1/4 size, each sample the mean of
 //                                  2x2 or 4x4 source samples (jpge_set_downscale; not with
-//                                  --gpus / --devices).
+//                                  --gpus / --devices);
+//   --orient none|flip-h|rot180|flip-v|transpose|rot90|transverse|rot270
+//                                  code the image flipped, rotated (rot90: clockwise) or
+//                                  transposed (jpge_set_orientation; not with --gpus /
+//                                  --devices, nor with --downscale 2|4).
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -58,6 +62,7 @@ int main(int argc, char* argv[]) {
     uint32_t restart = 0;
     int huffman = JPGE_HUFF_OPTIMAL;
     int downscale = 1;
+    int orient = JPGE_ORIENT_NONE;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-q") && i + 1 < argc) {
             quality = std::atoi(argv[++i]);
@@ -86,6 +91,16 @@ int main(int argc, char* argv[]) {
                 std::cerr << "jpgenc: --downscale takes 1, 2 or 4" << std::endl;
                 return 1;
             }
+        } else if (!std::strcmp(argv[i], "--orient") && i + 1 < argc) {
+            static const char* const names[8] = {"none", "flip-h", "rot180", "flip-v", "transpose", "rot90", "transverse", "rot270"};
+            const std::string m = argv[++i];
+            orient = -1;
+            for (int o = 0; o < 8; ++o)
+                if (m == names[o]) orient = o;
+            if (orient < 0) {
+                std::cerr << "jpgenc: --orient takes none, flip-h, rot180, flip-v, transpose, rot90, transverse or rot270" << std::endl;
+                return 1;
+            }
         } else {
             pos.emplace_back(argv[i]);
         }
@@ -99,12 +114,14 @@ int main(int argc, char* argv[]) {
         if (!devs.empty()) {
             if (huffman != JPGE_HUFF_OPTIMAL) throw std::runtime_error("--huffman standard: not for striped encodes");
             if (downscale != 1) throw std::runtime_error("--downscale: not for striped encodes");
+            if (orient != JPGE_ORIENT_NONE) throw std::runtime_error("--orient: not for striped encodes");
             return striped(devs, pos[0], jpg, quality, restart);
         }
         auto img = jpge::loadPPM(pos[0]);
         if (restart) jpge::detail::check(jpge_set_restart_interval(jpge::default_context(), restart), "restart");
         if (huffman) jpge::detail::check(jpge_set_huffman(jpge::default_context(), huffman, nullptr), "huffman");
         if (downscale != 1) jpge::detail::check(jpge_set_downscale(jpge::default_context(), downscale), "downscale");
+        if (orient != JPGE_ORIENT_NONE) jpge::detail::check(jpge_set_orientation(jpge::default_context(), orient), "orient");
         img.writeJPEG(jpg, quality);
     } catch (const std::exception& e) {
         std::cerr << "jpgenc: " << e.what() << std::endl;

@@ -299,6 +299,18 @@ int Encoder::downscale() {
     return ds_;
 }
 
+int Encoder::set_orientation(int o) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    if (!orient_valid(o)) return kErrArg;
+    orient_ = o;
+    return kOk;
+}
+
+int Encoder::orientation() {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    return orient_;
+}
+
 int Encoder::set_yuv_transform(int preset, const YuvXf* custom) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     YuvXf t;
@@ -612,6 +624,7 @@ FdctArgs Encoder::fdct_args(Slot& s, int maxval, Slot* imp) {
     a.fmt = s.in_fmt;
     a.plane_stride = s.in_plane_stride;
     a.ds = (uint32_t)s.ds;
+    a.orient = (uint32_t)s.orient;
     a.src_w = s.src_w;
     a.src_h = s.src_h;
     // the sample transform of Y, Cb, Cr and gray frames (FULL_601: the kExact instances)
@@ -714,8 +727,14 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     // the geometry of everything K1 writes is that of the frame of ceil(f / ds) pixels
     const int ds = ds_;
     if (ds > 1 && !ds_fmt(f.fmt)) return kErrArg;  // (the layouts without a downscaling kernel)
-    const uint32_t out_w = ds_dim(f.width, ds), out_h = ds_dim(f.height, ds);
+    // an oriented frame, likewise: f is the source, everything K1 writes is the oriented frame's
+    // (the layouts and modes without an oriented kernel; not together with a downscale)
+    const int orient = orient_;
+    if (orient && (!orient_fmt(f.fmt) || ds > 1)) return kErrArg;
+    const uint32_t out_w = orient ? orient_w(f.width, f.height, orient) : ds_dim(f.width, ds),
+                   out_h = orient ? orient_h(f.width, f.height, orient) : ds_dim(f.height, ds);
     const Geometry g = gray ? gray_geometry(out_w, out_h) : geometry(out_w, out_h, mode_);
+    if (orient_transposed(orient) && g.row8()) return kErrArg;  // (the transposed kernels are the 16x16-MCU ones)
     Geometry src = g;  // (the extent K1's offsets span)
     src.width = f.width;
     src.height = f.height;
@@ -778,7 +797,7 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     }
     s.begin(g, qy, qc, dev_in ? f.rgb : s.d_in, dev_in ? stride : dev_pitch, f.fmt,
             planes > 1 ? (dev_in ? plane_stride : dev_plane) : 0, dev_out ? f.out : s.d_out,
-            dev_out ? f.cap : s.cap_out, restart_mcus_, out_w, out_h, ds, ds > 1 ? f.width : 0, ds > 1 ? f.height : 0);
+            dev_out ? f.cap : s.cap_out, restart_mcus_, out_w, out_h, ds, ds > 1 || orient ? f.width : 0, ds > 1 || orient ? f.height : 0, orient);
     if (flags & kFlagFixedTables) {
         // fixed Huffman tables: the frame's own transform kernel carries its code words and
         // headers to the device, where they are new there
@@ -1080,7 +1099,7 @@ int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], ui
     // kFirstSleepMaxPixels: the helper spins from here to the histograms, which take
     // milliseconds there, for tables that are a small part of such a call.
     TableHelper* helper = nullptr;
-    const uint64_t npx = (uint64_t)ds_dim(f.width, ds_) * ds_dim(f.height, ds_);  // (the coded frame's)
+    const uint64_t npx = (uint64_t)ds_dim(f.width, ds_) * ds_dim(f.height, ds_);  // (the coded frame's; an oriented one's is the source's)
     if (!st && table_helper_ && lanes_.size() == 1 && npx >= (1u << 20) && npx <= kFirstSleepMaxPixels) {
         if (!helper_) helper_.reset(new TableHelper());
         helper = helper_.get();
@@ -1226,7 +1245,9 @@ int Encoder::batch_set_size(const FrameDesc* fr, int n) const {
     const bool placed_in_code = (ext_place_ > 0 || (ext_place_ < 0 && lanes_.size() > 1)) && place_in_code_;
     // (downscaled frames: one source size and one factor give one output geometry, which is
     // the one the kernels after K1 and the set's size go by)
-    const uint32_t w0 = ds_dim(f0.width, ds_), h0 = ds_dim(f0.height, ds_);
+    // (oriented frames: the oriented frame's, likewise; prep1 refuses both settings together)
+    const uint32_t w0 = orient_ ? orient_w(f0.width, f0.height, orient_) : ds_dim(f0.width, ds_),
+                   h0 = orient_ ? orient_h(f0.width, f0.height, orient_) : ds_dim(f0.height, ds_);
     const Geometry g0 = fmt_gray(f0.fmt) ? gray_geometry(w0, h0) : geometry(w0, h0, mode_);
     if (!placed_in_code || restart_mcus_ || layout(g0).grid() > kPlaceInCodeMaxWgs) return 1;
     if (set_) return set_;

@@ -162,6 +162,13 @@ class Encoder {
     int set_downscale(int factor);
     int downscale();
 
+    // Orientation of the following pixel encodes and stage entries (jpge.h jpge_set_orientation,
+    // JPGE_ORIENT_*): K1 reads the source flipped, rotated or transposed and codes the oriented
+    // frame.  RGB8, BGR8, RGBA8 and BGRA8; the transposed ones (4-7) in the 16x16-MCU modes; not
+    // with a downscale factor above 1; the stripe phases refuse it.  encode_planes ignores it.
+    int set_orientation(int o);
+    int orientation();
+
     int lanes() const { return (int)lanes_.size(); }
 
   private:
@@ -238,6 +245,7 @@ class Encoder {
     int mode_ = 420;            // subsampling mode (jpge_set_subsampling)
     int fmt_ = kFmtRgb8;        // input layout (jpge_set_input_format)
     int ds_ = 1;                // box downscale factor (jpge_set_downscale)
+    int orient_ = 0;            // orientation (jpge_set_orientation)
     // Huffman mode (jpge_set_huffman) and, in a fixed mode, the four tables: as given, as
     // codes, and as the [4][256] (len << 16) | code words the code kernel reads (built once,
     // at set_huffman); the generation numbers a setting (a slot remembers whose tables it holds)

@@ -160,6 +160,9 @@ struct Encoder::Slot {
     // and g, img_w, img_h and everything after K1 are the frame of ceil(src / ds) pixels
     int ds = 1;
     uint32_t src_w = 0, src_h = 0;
+    // orientation (jpge_set_orientation): non-zero: the input is the src_w x src_h source, and g,
+    // img_w, img_h and everything after K1 are the oriented frame
+    int orient = 0;
     uint8_t* out_dev = nullptr;
     size_t out_cap = 0;
     size_t hdr_len = 0;
@@ -206,8 +209,9 @@ struct Encoder::Slot {
     // keys and rst.mcu0.  (img_w, img_h: the header's dimensions.)
     void begin(const Geometry& geo, const uint8_t y[64], const uint8_t c[64], const uint8_t* in, size_t stride, int fmt,
                size_t plane_stride, uint8_t* out, size_t cap, uint32_t restart, uint32_t w, uint32_t h, int factor = 1,
-               uint32_t source_w = 0, uint32_t source_h = 0) {
+               uint32_t source_w = 0, uint32_t source_h = 0, int orientation = 0) {
         ds = factor;
+        orient = orientation;
         src_w = source_w;
         src_h = source_h;
         std::memcpy(qy, y, 64);

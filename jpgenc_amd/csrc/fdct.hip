@@ -221,6 +221,20 @@ static_assert(kDs == 1 || ((kDs == 2 || kDs == 4) && (kShape <= kShapeX4 || kSha
 constexpr uint32_t kDsBits = kDs == 4 ? 4u : kDs == 2 ? 2u : 0u;  // log2 of the samples of a mean
 constexpr uint32_t kDsHalf = (1u << kDsBits) >> 1;                // round half up
 constexpr uint32_t kSelRgbx = 0x0C020100u, kSelBgrx = 0x0C000102u;  // perm selectors of a 4-byte pixel (0x0c: zero)
+// The oriented builds (JPGE_K1_ORIENT 1..4, kernels.hpp orient_class; FdctArgs::orient) of the RGB8,
+// BGR8 and 4-byte shapes: g is the oriented frame O, read from the src_w x src_h source.  A lane
+// loads the same kRun bytes of one source row; what changes is which row and start column, the
+// order its 16 words are staged in (mirrored: reversed, a renaming of registers) and, transposed,
+// where they go: down a column of the staged tile ("oriented loads" in fdct_kernel).  Whether the
+// source's rows run backwards is a wave-uniform scalar of the frame (orient_rows_back).  The tile,
+// the staged words and everything after the staging are O's.  4-wave workgroups and frame sets only.
+#ifndef JPGE_K1_ORIENT
+#define JPGE_K1_ORIENT 0
+#endif
+constexpr int kOrient = JPGE_K1_ORIENT;
+static_assert(kOrient == 0 || (kOrient >= 1 && kOrient <= 4 && kDs == 1 && kShape <= kShapeX4), "JPGE_K1_ORIENT");
+constexpr bool kOrMirror = kOrient == 2 || kOrient == 4;  // the source's columns run backwards
+constexpr bool kOrTrans = kOrient >= 3;                   // O's rows are the source's columns (fdct_kernel only)
 
 // perm selector of a 3-byte pixel starting at byte o8 of a word pair
 __device__ __forceinline__ constexpr uint32_t sel3(uint32_t o8) {
@@ -796,6 +810,13 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         sh_ = a.src_h;
         asm volatile("" : "+s"(sw_), "+s"(sh_));
     }
+    uint32_t rows_back_ = 0;         // the oriented builds: the source's rows run backwards
+    if constexpr (kOrient != 0) {
+        sw_ = a.src_w;
+        sh_ = a.src_h;
+        rows_back_ = orient_rows_back((int)a.orient) ? 1u : 0u;
+        asm volatile("" : "+s"(sw_), "+s"(sh_), "+s"(rows_back_));
+    }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
     if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210 && !kV210)) {
@@ -825,6 +846,19 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010 || kShape == kShapeI210) || (stride_ & 31) == 0);
     const int r16 = lane >> 2, c16 = lane & 3;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;     // DCT: lane -> (block of the round, column)
+    // ---- oriented loads (kOrient != 0) ----
+    // Not transposed: the lane map stays, (r16, c16) is O's row y and columns xs .. xs + 15; the
+    // source row is y or sh - 1 - y, the run starts at source column xs, or sw - 16 - xs mirrored.
+    // Transposed: the 64x16 tile of O is a source block 16 pixels wide and 64 rows tall; lane l
+    // loads the run of the source row under O's column mcol0 * 16 + l (or sh - 1 - that), from
+    // source column mrow * 16 (mirrored: sw - 16 - mrow * 16), and stages it down column l.
+    // A mirrored run's bytes start 16-byte aligned only when the row's bytes are a multiple of 16.
+    const bool or_aligned = aligned && (!kOrMirror || ((kBpp * sw_) & 15u) == 0);
+    // pixel (oy, ox) of O, both inside it, by the clamped path's byte loads
+    auto or_pixel = [&](uint32_t oy, uint32_t ox) -> uint32_t {
+        const uint32_t r = kOrTrans ? ox : oy, c = kOrTrans ? oy : ox;
+        return edge_pixel(rgb_, stride_, ps_, sel4_, rows_back_ ? sh_ - 1 - r : r, kOrMirror ? sw_ - 1 - c : c);
+    };
 
     // Pixels and coefficients move through buffer descriptors: an out-of-range
     // offset (kOob) makes a load return zeros and drops a store, so every tile
@@ -876,6 +910,18 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * 4;
         const uint32_t y = mrow * 16 + r16, xs = mcol0 * 16 + c16 * 16;
+        if constexpr (kOrient != 0) {
+            // r: the source row before rows_back; c0: the run's first source column before the mirror.
+            // Fast: the run's 16 pixels of O and the lane's row (transposed: column) lie inside O.
+            const uint32_t ox = mcol0 * 16 + (uint32_t)lane;
+            const uint32_t r = kOrTrans ? ox : y, c0 = kOrTrans ? mrow * 16 : xs;
+            const bool in = kOrTrans ? ox < gw_ && mrow * 16 + 16 <= gh_ : y < gh_ && xs + 16 <= gw_;
+            const bool ok = k < n_p && or_aligned && in;
+            // (ok: r < sh and c0 + 16 <= sw, so the offset is inside the descriptor's range, below 2^32)
+            const uint32_t sr = rows_back_ ? sh_ - 1 - r : r, sc = kOrMirror ? sw_ - 16 - c0 : c0;
+            load_run(rgb_rs, ok ? sr * (uint32_t)stride_ + sc * kBpp : kOob, kOob, v0, v1, v2, v3);
+            return ok;
+        }
         bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
         // (I420: and the 16 chroma bytes lie inside their row)
         if constexpr (kShape == kShapeI420) ok = ok && ((xs >> 5) + 1) * 16 <= (gw_ + 1) / 2;
@@ -1114,18 +1160,36 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
                 px[i] = __builtin_amdgcn_perm(wd[d + 1], wd[d], sel3(o8));
             }
         }
+        if constexpr (kOrMirror) {  // the run in O's order: a renaming of registers
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const uint32_t t = px[i];
+                px[i] = px[15 - i];
+                px[15 - i] = t;
+            }
+        }
         if (!cfast) {  // right/bottom edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            if constexpr (kDs > 1)  // (of the downscaled frame, each pixel from its clamped source pixels)
+            if constexpr (kOrTrans)  // (O's coordinates clamped first, then mapped to the source)
+                for (int i = 0; i < 16; ++i) px[i] = or_pixel(min(mrow * 16 + i, gh_ - 1), min(mcol0 * 16 + (uint32_t)lane, gw_ - 1));
+            else if constexpr (kOrient != 0)
+                for (int i = 0; i < 16; ++i) px[i] = or_pixel(sy, min(xs + i, gw_ - 1));
+            else if constexpr (kDs > 1)  // (of the downscaled frame, each pixel from its clamped source pixels)
                 for (int i = 0; i < 16; ++i) px[i] = edge_ds(rgb_, stride_, ps_, sw_, sh_, sel4_, sy, min(xs + i, gw_ - 1));
             else if constexpr (kYuv)
                 for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sel4_, sy, min(xs + i, gw_ - 1));
             else
                 for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
-        uint32_t* dst = &W.rgbx[r16 * kRgbPitch + c16 * 16];
+        if constexpr (kOrTrans) {
+            // down column `lane` of the staged tile: the lanes' addresses are consecutive words
 #pragma unroll
-        for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
+            for (int i = 0; i < 16; ++i) W.rgbx[i * kRgbPitch + lane] = px[i];
+        } else {
+            uint32_t* dst = &W.rgbx[r16 * kRgbPitch + c16 * 16];
+#pragma unroll
+            for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
+        }
         wave_order();
         // prefetch the next tile of this wave (into the registers just staged) while
         // this one is transformed
@@ -1234,6 +1298,13 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
         sh_ = a.src_h;
         asm volatile("" : "+s"(sw_), "+s"(sh_));
     }
+    uint32_t rows_back_ = 0;         // the oriented builds: the source's rows run backwards
+    if constexpr (kOrient != 0) {
+        sw_ = a.src_w;
+        sh_ = a.src_h;
+        rows_back_ = orient_rows_back((int)a.orient) ? 1u : 0u;
+        asm volatile("" : "+s"(sw_), "+s"(sh_), "+s"(rows_back_));
+    }
     uint64_t ps_ = 0;                // planar: the plane pitch
     uint32_t sel4_ = kSelRgbx;       // 4-byte pixels: the byte selector of the channel order
     if constexpr (kShape == kShapePlanar || (kYuv && !kGray && !kPacked422 && kShape != kShapeY210 && !kV210)) {
@@ -1267,6 +1338,11 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
     const bool aligned = (((uintptr_t)rgb_ | stride_ | ps_) & 15) == 0 && (!(kHalfPitch || kShape == kShapeI010 || kShape == kShapeI210) || (stride_ & 31) == 0);
     const int r8 = lane >> 3, c8 = lane & 7;  // staging: lane -> (pixel row, 16-px chunk)
     const int b8 = lane >> 3, j = lane & 7;   // DCT: lane -> (block of the round, column)
+    // (the oriented builds that are not transposed, as in fdct_kernel)
+    const bool or_aligned = aligned && (!kOrMirror || ((kBpp * sw_) & 15u) == 0);
+    auto or_pixel = [&](uint32_t oy, uint32_t ox) -> uint32_t {
+        return edge_pixel(rgb_, stride_, ps_, sel4_, rows_back_ ? sh_ - 1 - oy : oy, kOrMirror ? sw_ - 1 - ox : ox);
+    };
 
     const RgbRsrc rgb_rs = rgb_rsrc(rgb_, stride_, ps_, sw_, sh_);
     const __amdgpu_buffer_rsrc_t coef_rs =
@@ -1298,6 +1374,12 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * kMcus;
         const uint32_t y = mrow * 8 + r8, xs = mcol0 * 8 * kYh + c8 * 16;
+        if constexpr (kOrient != 0) {
+            const bool ok = k < n_p && or_aligned && y < gh_ && xs + 16 <= gw_;
+            const uint32_t sr = rows_back_ ? sh_ - 1 - y : y, sc = kOrMirror ? sw_ - 16 - xs : xs;
+            load_run(rgb_rs, ok ? sr * (uint32_t)stride_ + sc * kBpp : kOob, kOob, v0, v1, v2, v3);
+            return ok;
+        }
         bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
         // (I422: and the 16 chroma bytes lie inside their row)
         if constexpr (kShape == kShapeI422) ok = ok && ((xs >> 5) + 1) * 16 <= (gw_ + 1) / 2;
@@ -1409,9 +1491,19 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
                 px[i] = __builtin_amdgcn_perm(wd[d + 1], wd[d], sel3(o8));
             }
         }
+        if constexpr (kOrMirror) {  // the run in O's order: a renaming of registers
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const uint32_t t = px[i];
+                px[i] = px[15 - i];
+                px[15 - i] = t;
+            }
+        }
         if (!cfast) {  // edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
-            if constexpr (kDs > 1)
+            if constexpr (kOrient != 0)  // (O's coordinates clamped first, then mapped to the source)
+                for (int i = 0; i < 16; ++i) px[i] = or_pixel(sy, min(xs + i, gw_ - 1));
+            else if constexpr (kDs > 1)
                 for (int i = 0; i < 16; ++i) px[i] = edge_ds(rgb_, stride_, ps_, sw_, sh_, sel4_, sy, min(xs + i, gw_ - 1));
             else if constexpr (kYuv)
                 for (int i = 0; i < 16; ++i) px[i] = edge_yuv(rgb_, stride_, ps_, gh_, sel4_, sy, min(xs + i, gw_ - 1));
@@ -1508,14 +1600,17 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
 // tiles per wave.
 constexpr uint32_t kK1WholeCuTiles = 65536;
 uint32_t k1_tiles(const Geometry& g);
-bool k1_whole_cu(const Geometry& g, bool solo, uint32_t ds = 1);
-#if JPGE_K1_SHAPE == 0 && JPGE_K1_DS == 1
+bool k1_whole_cu(const Geometry& g, bool solo, uint32_t ds = 1, uint32_t orient = 0);
+#if JPGE_K1_SHAPE == 0 && JPGE_K1_DS == 1 && JPGE_K1_ORIENT == 0
 uint32_t k1_tiles(const Geometry& g) {
     const uint32_t per = g.row8() ? 16 / g.yh : 4;  // MCUs per tile
     return ((g.mw + per - 1) / per) * g.mh;
 }
-// (a downscaled frame, ds > 1: always the 4-wave shape, whose registers hold the reduction without spilling)
-bool k1_whole_cu(const Geometry& g, bool solo, uint32_t ds) { return solo && ds <= 1 && k1_tiles(g) >= kK1WholeCuTiles; }
+// (a downscaled frame, ds > 1: always the 4-wave shape, whose registers hold the reduction without spilling;
+// an oriented frame, orient != 0: likewise, its builds have no other)
+bool k1_whole_cu(const Geometry& g, bool solo, uint32_t ds, uint32_t orient) {
+    return solo && ds <= 1 && orient == 0 && k1_tiles(g) >= kK1WholeCuTiles;
+}
 #endif
 
 // (static, like the kernels: every load shape's build has its own)
@@ -1530,8 +1625,8 @@ static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, h
         if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     } else {
-        // (the downscaling builds have the 4-wave workgroup only: k1_whole_cu is false for them)
-        if constexpr (kDs == 1) {
+        // (the downscaling and the oriented builds have the 4-wave workgroup only: k1_whole_cu is false for them)
+        if constexpr (kDs == 1 && kOrient == 0) {
             if (k1_whole_cu(a.g, a.solo)) {
                 if (ex) return launch_timed(t, fdct_row8_kernel<true, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
                 else return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
@@ -1553,8 +1648,8 @@ static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hi
         if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     } else {
-        // (the downscaling builds have the 4-wave workgroup only: k1_whole_cu is false for them)
-        if constexpr (kDs == 1) {
+        // (the downscaling and the oriented builds have the 4-wave workgroup only: k1_whole_cu is false for them)
+        if constexpr (kDs == 1 && kOrient == 0) {
             if (k1_whole_cu(a.g, a.solo)) {
                 if (ex) return launch_timed(t, fdct_kernel<true, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
                 else return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
@@ -1581,7 +1676,9 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
         return launch_420<kFiltS420, kN>(fs, grid, s, t);
     } else {
         if (a.g.row8()) {
-            switch (a.g.yh) {
+            // (the transposed builds have fdct_kernel only)
+            if constexpr (kOrTrans) return hipErrorInvalidValue;
+            else switch (a.g.yh) {
                 // (launch_timed returns the launch's error: hipGetLastError has already consumed it)
                 case 1: return a.g.bpm != 3 ? hipErrorInvalidValue : launch_row8<1, kN>(fs, grid, s, t);
                 case 2: return a.g.bpm != 4 ? hipErrorInvalidValue : launch_row8<2, kN>(fs, grid, s, t);
@@ -1599,9 +1696,10 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
     }
 }
 
-#if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1
+#if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1 || JPGE_K1_ORIENT != 0
 // this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
-// _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210 / _v210; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...)
+// _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210 / _v210; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...;
+// the oriented builds: launch_fdct_rgb8_o1 .. _o4, _bgr8_o1, ...)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
@@ -1645,10 +1743,20 @@ hipError_t launch_fdct_x4_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t gri
 hipError_t launch_fdct_x4_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_nv12_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_nv12_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+// the oriented builds (FdctArgs::orient, kernels.hpp orient_class 1..4) of the shapes that have them
+#define JPGE_K1_ORIENT_ENTRIES(shape)                                                                                  \
+    hipError_t launch_fdct_##shape##_o1(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t); \
+    hipError_t launch_fdct_##shape##_o2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t); \
+    hipError_t launch_fdct_##shape##_o3(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t); \
+    hipError_t launch_fdct_##shape##_o4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+JPGE_K1_ORIENT_ENTRIES(rgb8)
+JPGE_K1_ORIENT_ENTRIES(bgr8)
+JPGE_K1_ORIENT_ENTRIES(x4)
+#undef JPGE_K1_ORIENT_ENTRIES
 
-uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs, uint32_t ds) {
+uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs, uint32_t ds, uint32_t orient) {
     const uint32_t tiles = k1_tiles(g);
-    if (k1_whole_cu(g, solo, ds)) {  // one whole-CU workgroup per CU (MI355X: 256 CUs)
+    if (k1_whole_cu(g, solo, ds, orient)) {  // one whole-CU workgroup per CU (MI355X: 256 CUs)
         const uint32_t cap = 256u * (16u / (uint32_t)kK1WavesSolo);
         return tiles < cap ? tiles : cap;
     }
@@ -1683,20 +1791,32 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
             src.width = m.src_w;
             src.height = m.src_h;
         }
+        // an oriented frame: g is O's; the offsets span the source.  The interleaved RGB layouts, no
+        // downscale; the transposed orientations in the 16x16-MCU modes.  A set shares one
+        // orientation and one source size.
+        if (m.orient) {
+            if (!orient_valid((int)m.orient) || !orient_fmt(m.fmt) || m.ds > 1 || !m.src_w || !m.src_h ||
+                m.g.width != orient_w(m.src_w, m.src_h, (int)m.orient) || m.g.height != orient_h(m.src_w, m.src_h, (int)m.orient) ||
+                (orient_transposed((int)m.orient) && m.g.row8()))
+                return hipErrorInvalidValue;
+            src.width = m.src_w;
+            src.height = m.src_h;
+        }
         if (!k1_offsets_fit(m.fmt, src, m.stride)) return hipErrorInvalidValue;
         if ((m.ds > 1 ? m.ds : 1u) != (a.ds > 1 ? a.ds : 1u) || (m.ds > 1 && (m.src_w != a.src_w || m.src_h != a.src_h)))
             return hipErrorInvalidValue;
+        if (m.orient != a.orient || (m.orient && (m.src_w != a.src_w || m.src_h != a.src_h))) return hipErrorInvalidValue;
         // 10-bit layouts: 16-bit words (even addresses and pitches), and always the sample transform
         if (fmt_yuv10(m.fmt) && ((((uintptr_t)m.rgb | m.stride | m.plane_stride) & 1) || !m.xf_on)) return hipErrorInvalidValue;
         // (v210: 32-bit words, one plane, no downscaling build)
         if (m.fmt == kFmtV210 && ((((uintptr_t)m.rgb | m.stride) & 3) || m.plane_stride)) return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
             fmt_shape(m.fmt) != fmt_shape(a.fmt) || (m.xf_on != 0) != (a.xf_on != 0) ||
-            m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs, m.ds))
+            m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs, m.ds, m.orient))
             return hipErrorInvalidValue;
     }
     const uint32_t grid = fs.wg0[fs.n];
-    if (a.ds <= 1 && fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
+    if (a.ds <= 1 && !a.orient && fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
     if constexpr (kN == 1) {
         if (fmt_shape(a.fmt) == kShapeP010) return launch_fdct_p010_one(fs, grid, s, t);
         if (fmt_shape(a.fmt) == kShapeI010) return launch_fdct_i010_one(fs, grid, s, t);
@@ -1710,6 +1830,15 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
     w.n = fs.n;
     for (uint32_t f = 0; f < fs.n; ++f) w.a[f] = fs.a[f];
     for (uint32_t f = 0; f <= fs.n; ++f) w.wg0[f] = fs.wg0[f];
+    if (a.orient) {
+        const int c = orient_class((int)a.orient);
+        switch (fmt_shape(a.fmt)) {
+            case kShapeRgb8: return c == 1 ? launch_fdct_rgb8_o1(w, grid, s, t) : c == 2 ? launch_fdct_rgb8_o2(w, grid, s, t) : c == 3 ? launch_fdct_rgb8_o3(w, grid, s, t) : launch_fdct_rgb8_o4(w, grid, s, t);
+            case kShapeBgr8: return c == 1 ? launch_fdct_bgr8_o1(w, grid, s, t) : c == 2 ? launch_fdct_bgr8_o2(w, grid, s, t) : c == 3 ? launch_fdct_bgr8_o3(w, grid, s, t) : launch_fdct_bgr8_o4(w, grid, s, t);
+            case kShapeX4: return c == 1 ? launch_fdct_x4_o1(w, grid, s, t) : c == 2 ? launch_fdct_x4_o2(w, grid, s, t) : c == 3 ? launch_fdct_x4_o3(w, grid, s, t) : launch_fdct_x4_o4(w, grid, s, t);
+            default: return hipErrorInvalidValue;
+        }
+    }
     if (a.ds > 1) {
         const bool d2 = a.ds == 2;
         switch (fmt_shape(a.fmt)) {
@@ -1741,12 +1870,12 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
 }
 
 hipError_t launch_fdct(const FdctArgs& a, hipStream_t s, const KTimer* t) {
-    return launch_fdct_fs(frame_set<1>(&a, 1, fdct_grid(a.g, a.solo, a.wgs, a.ds)), s, t);
+    return launch_fdct_fs(frame_set<1>(&a, 1, fdct_grid(a.g, a.solo, a.wgs, a.ds, a.orient)), s, t);
 }
 
 hipError_t launch_fdct_set(const FdctArgs* a, int n, hipStream_t s, const KTimer* t) {
     if (n < 1 || n > kMaxSet) return hipErrorInvalidValue;
-    return launch_fdct_fs(frame_set(a, n, fdct_grid(a[0].g, a[0].solo, a[0].wgs, a[0].ds)), s, t);
+    return launch_fdct_fs(frame_set(a, n, fdct_grid(a[0].g, a[0].solo, a[0].wgs, a[0].ds, a[0].orient)), s, t);
 }
 #endif  // JPGE_K1_SHAPE == 0
 

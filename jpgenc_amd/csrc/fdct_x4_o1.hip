@@ -1,0 +1,5 @@
+// K1 for 4-byte pixels (RGBA8, BGRA8), oriented, source rows forwards or backwards, columns as they are (JPGE_ORIENT_FLIP_V): fdct.hip built with that load shape and orientation class (see "oriented loads" there).
+#define JPGE_K1_SHAPE 2
+#define JPGE_K1_ORIENT 1
+#define JPGE_K1_ENTRY launch_fdct_x4_o1
+#include "fdct.hip"

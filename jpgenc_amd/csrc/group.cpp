@@ -294,6 +294,10 @@ int jpge_group_encode_striped(jpge_group* g, const uint8_t* rgb, uint32_t width,
         int factor = 1;
         if (const int st = jpge_get_downscale(c, &factor)) return st;
         if (factor != 1) return (int)JPGE_E_ARG;
+        // and as it lies (the stripe phases refuse an orientation)
+        int orient = JPGE_ORIENT_NONE;
+        if (const int st = jpge_get_orientation(c, &orient)) return st;
+        if (orient != JPGE_ORIENT_NONE) return (int)JPGE_E_ARG;
     }
     const size_t row = (size_t)width * 3, pitch = stride ? stride : row;
     if (pitch < row) return (int)JPGE_E_ARG;

@@ -208,7 +208,8 @@ int encode_files(Encoder& enc, std::unique_ptr<IngestBuffers, IngestBuffersDelet
         for (int k = 0; k < cnt; ++k) {
             if (status[i0 + k]) continue;
             FrameDesc f = desc[s][k];
-            const size_t cap = Encoder::max_jpeg_bytes(f.width, f.height);
+            // (either way up: the context's orientation may transpose the frame)
+            const size_t cap = std::max(Encoder::max_jpeg_bytes(f.width, f.height), Encoder::max_jpeg_bytes(f.height, f.width));
             if (const int r = dout[s][k].reserve(cap)) {
                 status[i0 + k] = r;
                 continue;

@@ -336,7 +336,8 @@ std::vector<uint8_t> Image::encode(int quality) const {
     std::vector<uint8_t> out;
     size_t len = 0;
     if (src_valid_ && color_space_type == RGB) {  // the RGB8 frame: the fused kernels
-        out.resize(jpge_max_jpeg_bytes(real_width, real_height));
+        // (either way up: the context's orientation may transpose the frame)
+        out.resize(std::max(jpge_max_jpeg_bytes(real_width, real_height), jpge_max_jpeg_bytes(real_height, real_width)));
         check(jpge_encode_rgb8(default_context(), src_->data(), real_width, real_height, 0, maxval_, qy, qc,
                                out.data(), out.size(), &len, 0),
               "writeJPEG");

@@ -180,6 +180,10 @@ struct FdctArgs {
     // (in the padding before q, src_w and src_h in the padding before xf: no field moves, and
     // the block keeps its size)
     uint32_t ds = 1;
+    // orientation (jpge_set_orientation, kOrient* below): non-zero = g is the oriented frame O, read
+    // from the src_w x src_h frame at rgb (the oriented load shapes, fdct.hip JPGE_K1_ORIENT).
+    // (in the last padding word before q)
+    uint32_t orient = 0;
     // luma then chroma quantisers, natural order (bytes: a small kernarg block; 16-byte
     // aligned so the kernels fetch it with scalar loads, see fdct.hip q_entry)
     alignas(16) uint8_t q[128];
@@ -200,19 +204,45 @@ struct FdctArgs {
     // (in the padding after fmt; xf at the block's end: no earlier field moves)
     uint32_t xf_on = 0;
     uint64_t plane_stride = 0;
-    uint32_t src_w = 0, src_h = 0;  // ds > 1: the source frame's size (stride and plane_stride are its pitches)
+    uint32_t src_w = 0, src_h = 0;  // ds > 1 or orient != 0: the source frame's size (stride and plane_stride are its pitches)
     // y_off, m0..m6 (host_io.hpp YuvXf); fetched with scalar loads, like q
     alignas(16) double xf[8] = {0, 1, 0, 0, 1, 0, 0, 1};
 };
 
 static_assert(sizeof(FdctArgs) == 336 && offsetof(FdctArgs, q) == 64 && offsetof(FdctArgs, xf) == 272,
               "the downscale fields sit in padding: the argument block's layout is unchanged");
+static_assert(offsetof(FdctArgs, ds) == 56 && offsetof(FdctArgs, orient) == 60, "the orientation sits in padding too");
 
 // Box downscale by 2 or 4 inside K1 (jpge.h jpge_set_downscale): the interleaved RGB layouts in
 // every subsampling mode, and NV12 (whose Cb,Cr plane is averaged in its own domain).
 JPGE_HD inline bool ds_valid(int ds) { return ds == 1 || ds == 2 || ds == 4; }
 JPGE_HD inline bool ds_fmt(int fmt) { return (fmt >= kFmtRgb8 && fmt <= kFmtBgra8) || fmt == kFmtNv12; }
 JPGE_HD inline uint32_t ds_dim(uint32_t n, int ds) { return (n + (uint32_t)ds - 1) / (uint32_t)ds; }
+
+// Orientation applied inside K1 (jpge.h jpge_set_orientation, the same values): the coded frame
+// O of a sw x sh source S.  Three properties describe all eight: transposed (O is sh x sw and its
+// rows are the source's columns), mirrored (the source's columns run backwards) and rows_back (the
+// source's rows run backwards).  The interleaved RGB layouts only; 4-7 in the 16x16-MCU modes only.
+constexpr int kOrientNone = 0, kOrientFlipH = 1, kOrientRot180 = 2, kOrientFlipV = 3, kOrientTranspose = 4,
+              kOrientRot90 = 5, kOrientTransverse = 6, kOrientRot270 = 7;
+JPGE_HD inline bool orient_valid(int o) { return o >= 0 && o <= 7; }
+JPGE_HD inline bool orient_transposed(int o) { return o >= 4; }
+JPGE_HD inline bool orient_mirrored(int o) { return ((0xC6u >> o) & 1u) != 0; }   // 1, 2, 6, 7
+JPGE_HD inline bool orient_rows_back(int o) { return ((0x6Cu >> o) & 1u) != 0; }  // 2, 3, 5, 6
+JPGE_HD inline bool orient_fmt(int fmt) { return fmt >= kFmtRgb8 && fmt <= kFmtBgra8; }
+JPGE_HD inline uint32_t orient_w(uint32_t w, uint32_t h, int o) { return orient_transposed(o) ? h : w; }
+JPGE_HD inline uint32_t orient_h(uint32_t w, uint32_t h, int o) { return orient_transposed(o) ? w : h; }
+// the source pixel (row sr, column sc) of O(y, x)
+JPGE_HD inline void orient_src(int o, uint32_t sw, uint32_t sh, uint32_t y, uint32_t x, uint32_t& sr, uint32_t& sc) {
+    const uint32_t r = orient_transposed(o) ? x : y, c = orient_transposed(o) ? y : x;
+    sr = orient_rows_back(o) ? sh - 1 - r : r;
+    sc = orient_mirrored(o) ? sw - 1 - c : c;
+}
+// K1's build for an orientation (fdct.hip JPGE_K1_ORIENT): 0 none, 1 rows (3), 2 mirrored (1, 2),
+// 3 transposed (4, 5), 4 transposed and mirrored (6, 7); rows_back is a run-time scalar in each
+JPGE_HD inline int orient_class(int o) {
+    return o == 0 ? 0 : orient_transposed(o) ? (orient_mirrored(o) ? 4 : 3) : (orient_mirrored(o) ? 2 : 1);
+}
 
 // Stripe context of a frame (a row stripe of a larger image); the
 // defaults describe a whole frame.
@@ -474,8 +504,9 @@ inline FrameSet<A, N> frame_set(const A* a, int n, uint32_t grid_each) {
     return s;
 }
 
-// (ds: FdctArgs::ds, a downscaled frame runs the 4-wave workgroups at every size)
-uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs = 0, uint32_t ds = 1);
+// (ds: FdctArgs::ds, a downscaled frame runs the 4-wave workgroups at every size; orient:
+// FdctArgs::orient, an oriented frame likewise)
+uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs = 0, uint32_t ds = 1, uint32_t orient = 0);
 // statistics workgroups: wgs (0: 3 per CU), within the tile-table bound and the tile count
 uint32_t stats_grid(const SegLayout& L, uint32_t wgs = 0);
 // entropy partition of a frame: restart_mcus = 0 -> one segment over 128-block tiles

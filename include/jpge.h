@@ -286,6 +286,46 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * pointer and the stride 16-byte aligned. */
 #define JPGE_FMT_GRAY8 8
 
+/* 8-bit Bayer mosaics (an addition): what machine-vision and embedded sensors deliver (GenICam
+ * BayerRG8 / BayerGR8 / BayerGB8 / BayerBG8, V4L2 SRGGB8 / SGRBG8 / SGBRG8 / SBGGR8), white balance
+ * and gamma already applied in the camera.  One plane of `height` rows of `width` bytes, pitch
+ * `stride` (0 = width), plane_stride 0.  The name gives the colours of the 2x2 cell at rows 0-1,
+ * columns 0-1, read row by row (RGGB: row 0 is R,G and row 1 is G,B); the site at (y, x) has colour
+ * cell[y & 1][x & 1].
+ *
+ * The frame codes as the RGB8 frame D = jpge_demosaic_frame(frame), a bilinear demosaic in integers
+ * built inside the transform kernel as it stages a tile (no pass writes D):
+ *   V(y, x) is the raw byte at coordinates reflected without repeating the edge, i < 0 -> -i and
+ *   i >= n -> 2 (n - 1) - i, which keeps a site's colour parity.
+ *   At an R or B site:  own colour = V(y, x)
+ *                       G = (V(y-1,x) + V(y+1,x) + V(y,x-1) + V(y,x+1) + 2) >> 2
+ *                       the opposite colour = (V(y-1,x-1) + V(y-1,x+1) + V(y+1,x-1) + V(y+1,x+1) + 2) >> 2
+ *   At a G site:        G = V(y, x)
+ *                       the colour of its row's other sites = (V(y,x-1) + V(y,x+1) + 1) >> 1
+ *                       the colour of its column's other sites = (V(y-1,x) + V(y+1,x) + 1) >> 1
+ * The .jpg is, byte for byte, that of D coded as JPGE_FMT_RGB8 on the same context, under every
+ * other setting (quality tables, the six subsampling modes, restart interval, Huffman mode, frame
+ * sets and lanes, jpge_encode_batch, jpge_group_encode_batch); jpge_fdct_quant and
+ * jpge_symbol_stats return D's coefficients and histograms.  Padding to whole MCUs replicates D's
+ * right and bottom edge pixels: a coordinate is clamped in D first, and the clamped pixel is then
+ * demosaiced with its reflected neighbours.
+ * JPGE_E_ARG, before anything is queued (a batch: the frame's status): width or height below 2,
+ * maxval other than 255, a plane_stride other than 0, a downscale factor above 1, an orientation
+ * other than JPGE_ORIENT_NONE, jpge_stripe_transform and jpge_group_encode_striped.
+ * jpge_encode_planes and the plane stages ignore the layout.  The fast path needs the pointer and
+ * the stride 16-byte aligned.  Not built: other demosaic filters, deeper or packed raw, white
+ * balance, colour matrix and gamma. */
+#define JPGE_FMT_BAYER_RGGB8 10
+#define JPGE_FMT_BAYER_GRBG8 11
+#define JPGE_FMT_BAYER_GBRG8 12
+#define JPGE_FMT_BAYER_BGGR8 13
+/* The rule above in plain C++ on the host: the `height` rows of `width` raw bytes at `src`, pitch
+ * `stride` (0 = width), in Bayer layout `format`, to the RGB8 frame D at dst_rgb8, pitch dst_stride
+ * (0 = 3 * width).  JPGE_E_ARG: another layout, a dimension below 2, a NULL pointer, or a stride
+ * below a row's bytes; a refused call writes nothing.  (An addition.) */
+int jpge_demosaic_frame(int format, const uint8_t* src, uint32_t width, uint32_t height, size_t stride,
+                        uint8_t* dst_rgb8, size_t dst_stride);
+
 /* Input layout for the context's following jpge_encode_rgb8, jpge_encode_batch,
  * jpge_fdct_quant and jpge_symbol_stats calls (their `rgb` then points at a frame in
  * that layout), also on a group member's context (jpge_group_context), and so for
@@ -298,7 +338,7 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * The PPM entries (jpge_encode_file, jpge_encode_files) and the fp64 plane entries
  * ignore the setting.  jpge_stripe_transform takes the four interleaved layouts (the
  * stripe pointer stays "first pixel row of the stripe") and returns JPGE_E_ARG for
- * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts, the two 10-bit 4:2:0 and the three 10-bit 4:2:2 layouts, v210 and for
+ * the planar ones (RGB8_PLANAR, NV12, I420, YUV444_PLANAR), for the four 4:2:2 layouts, the two 10-bit 4:2:0 and the three 10-bit 4:2:2 layouts, v210, the four Bayer layouts and for
  * JPGE_FMT_GRAY8 (stripes are three-component 4:2:0 of interleaved colour); jpge_group_encode_striped needs JPGE_FMT_RGB8. */
 int jpge_set_input_format(jpge_ctx* ctx, int format, size_t plane_stride);
 /* the current setting (plane_stride may be NULL) */

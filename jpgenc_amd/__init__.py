@@ -51,6 +51,13 @@ JPGE_FMT_YUYV, JPGE_FMT_UYVY, JPGE_FMT_NV16, JPGE_FMT_I422 = 20, 21, 22, 23
 #: one (H, W) plane of 8-bit luminance -> a one-component (grayscale) JPEG; no chroma: the
 #: chroma table and the subsampling mode do not enter
 JPGE_FMT_GRAY8 = 8
+#: 8-bit Bayer mosaics (jpge.h): one (H, W) plane of raw bytes, the name the colours of the 2x2
+#: cell at rows 0-1, columns 0-1; coded as the RGB8 frame demosaic_frame returns
+JPGE_FMT_BAYER_RGGB8, JPGE_FMT_BAYER_GRBG8, JPGE_FMT_BAYER_GBRG8, JPGE_FMT_BAYER_BGGR8 = 10, 11, 12, 13
+#: the Bayer layouts by their encode_tensor(layout=...) names
+BAYER_LAYOUTS = {"bayer_rggb": JPGE_FMT_BAYER_RGGB8, "bayer_grbg": JPGE_FMT_BAYER_GRBG8,
+                 "bayer_gbrg": JPGE_FMT_BAYER_GBRG8, "bayer_bggr": JPGE_FMT_BAYER_BGGR8}
+_BAYER = frozenset(BAYER_LAYOUTS.values())
 
 #: Huffman modes (jpge.h JPGE_HUFF_*): per-image tables (the reference's stream, the default),
 #: the ITU T.81 Annex K tables, or the caller's four tables
@@ -74,7 +81,7 @@ STATUS = {
 EXPORTS = (
     "jpge_strerror", "jpge_version", "jpge_device_count", "jpge_open", "jpge_open_ex", "jpge_close", "jpge_set_timing",
     "jpge_get_timing", "jpge_reset_timing", "jpge_get_lanes", "jpge_set_restart_interval", "jpge_set_subsampling",
-    "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info",
+    "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info", "jpge_demosaic_frame",
     "jpge_v210_row_bytes", "jpge_v210_unpack",
     "jpge_set_huffman", "jpge_get_huffman", "jpge_standard_huffman",
     "jpge_set_yuv_transform", "jpge_get_yuv_transform", "jpge_yuv_preset",
@@ -234,6 +241,7 @@ def lib() -> ctypes.CDLL:
         L.jpge_get_orientation.argtypes = [vp, ctypes.POINTER(i32)]
         L.jpge_oriented_size.argtypes = [u32, u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
         L.jpge_orient_frame.argtypes = [i32, vp, u32, u32, sz, i32, vp, sz]
+        L.jpge_demosaic_frame.argtypes = [i32, vp, u32, u32, sz, vp, sz]
         L.jpge_device_count.argtypes = [ctypes.POINTER(i32)]
         L.jpge_max_jpeg_bytes.restype = sz
         L.jpge_max_jpeg_bytes.argtypes = [u32, u32]
@@ -752,10 +760,10 @@ def _frame_geom(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
 
 def _frame_geom_any(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
     bpp, planes = input_format_info(fmt)
-    if fmt == JPGE_FMT_GRAY8:
+    if fmt == JPGE_FMT_GRAY8 or fmt in _BAYER:  # one plane of bytes
         if a.ndim != 2 or a.dtype != np.uint8 or a.size == 0:
-            raise ValueError(f"frame of shape {a.shape} and type {a.dtype}: input layout {fmt} (GRAY8) takes "
-                             "a non-empty (H, W) uint8 array")
+            raise ValueError(f"frame of shape {a.shape} and type {a.dtype}: input layout {fmt} "
+                             f"({'GRAY8' if fmt == JPGE_FMT_GRAY8 else 'Bayer'}) takes a non-empty (H, W) uint8 array")
         return a.shape[1], a.shape[0], a.shape[1]
     if fmt in _YUV:
         if getattr(a, "fmt", None) != fmt or a.ndim != 1 or a.dtype != np.uint8 or \
@@ -775,7 +783,7 @@ def _frame_geom_any(a: np.ndarray, fmt: int) -> tuple[int, int, int]:
 
 def _as_frame(a, fmt: int):
     """(C-contiguous uint8 array, width, height, stride) of a frame for layout `fmt`."""
-    if fmt == JPGE_FMT_GRAY8:
+    if fmt == JPGE_FMT_GRAY8 or fmt in _BAYER:
         a = np.ascontiguousarray(a)  # (the type is checked, not converted: a float plane is no gray frame)
     elif fmt not in _YUV and fmt != JPGE_FMT_V210:
         a = np.ascontiguousarray(a, np.uint8)
@@ -885,6 +893,18 @@ def orient_frame(a, fmt: int, o: int):
     return out
 
 
+def demosaic_frame(a, fmt: int):
+    """The (H, W, 3) RGB8 frame an encode codes for the (H, W) uint8 Bayer mosaic `a` in layout
+    `fmt` (JPGE_FMT_BAYER_*): the bilinear rule of jpge.h on the host (jpge_demosaic_frame)."""
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError(f"frame of shape {a.shape} and type {a.dtype}: a Bayer mosaic is an (H, W) uint8 array")
+    h, w = a.shape
+    out = np.zeros((h, w, 3), np.uint8)
+    _check(lib().jpge_demosaic_frame(int(fmt), _p(a), w, h, w, _p(out), 3 * w), "demosaic_frame")
+    return out
+
+
 def device_count() -> int:
     n = ctypes.c_int(0)
     lib().jpge_device_count(ctypes.byref(n))
@@ -978,7 +998,7 @@ class Encoder:
         (H, W, 4) or, planar, (3, H, W); GRAY8: (H, W), written as a one-component JPEG;
         NV12 and I420: pack_yuv420 frames; YUYV, UYVY, NV16 and I422: pack_yuv422 frames; P010 and
         I010: pack_yuv420p10 frames; Y210, P210 and I210: pack_yuv422p10 frames; V210: pack_v210
-        frames.  plane_stride:
+        frames; BAYER_*: (H, W) mosaics of raw bytes, coded as demosaic_frame's RGB8 frame.  plane_stride:
         bytes between the planes of the raw-pointer entries' planar frames (NV12, I420: from
         the Y plane to the chroma, as for NV16 and I422; 0 = stride * height; the packed 4:2:2
         layouts are one plane and take 0)."""
@@ -1129,9 +1149,14 @@ class Encoder:
         bytes, or, with `out` a uint8 tensor on the frame's device, writes them there and
         returns their length.  The encoder's input layout is the same afterwards.
         layout: "chw" or "hwc"; needed only for a (3, H, 3) or (3, H, 4) tensor, which
-        could be either (else ValueError)."""
-        if layout not in (None, "chw", "hwc"):
+        could be either (else ValueError).  "bayer_rggb", "bayer_grbg", "bayer_gbrg" or
+        "bayer_bggr" (BAYER_LAYOUTS): the (H, W) tensor is a Bayer mosaic of raw bytes
+        (JPGE_FMT_BAYER_*), coded as the RGB8 frame demosaic_frame returns."""
+        bayer = BAYER_LAYOUTS.get(layout) if isinstance(layout, str) else None
+        if layout not in (None, "chw", "hwc") and bayer is None:
             raise ValueError(f"layout {layout!r}: 'chw' or 'hwc'")
+        if bayer is not None and t.dim() != 2:
+            raise ValueError(f"layout {layout!r} takes a 2-dimensional (H, W) uint8 tensor of raw bytes")
         if order not in ("rgb", "bgr"):
             raise ValueError(f"order {order!r}: 'rgb' or 'bgr'")
         if t.dim() not in (2, 3) or t.element_size() != 1 or t.dtype.is_floating_point:
@@ -1142,14 +1167,14 @@ class Encoder:
         hwc, chw = not gray and shape[2] in (3, 4), not gray and shape[0] == 3
         if hwc and chw and layout is None:
             raise ValueError(f"tensor of shape {shape} is (3, H, W) or (H, W, C): pass layout='chw' or 'hwc'")
-        if layout is not None:
+        if layout is not None and bayer is None:
             hwc, chw = hwc and layout == "hwc", chw and layout == "chw"
         if gray:  # (H, W)
             if shape[0] == 0 or shape[1] == 0:
                 raise ValueError(f"tensor of shape {shape}: an empty frame")
             if st[1] != 1 and shape[1] > 1:
                 raise ValueError(f"strides {st}: the inner dimension must have unit stride")
-            h, w, stride, fmt = shape[0], shape[1], st[0], JPGE_FMT_GRAY8
+            h, w, stride, fmt = shape[0], shape[1], st[0], JPGE_FMT_GRAY8 if bayer is None else bayer
             if h == 1:
                 stride = w  # (one row: any pitch)
         elif hwc:  # (H, W, C)

@@ -180,7 +180,7 @@ const char* jpge_strerror(int s) {
     }
 }
 
-int jpge_version(void) { return 106; }
+int jpge_version(void) { return 107; }
 
 int jpge_device_count(int* n) {
     if (!n) return JPGE_E_ARG;
@@ -426,6 +426,30 @@ int jpge_orient_frame(int format, const uint8_t* src, uint32_t w, uint32_t h, si
             jpge::orient_src(o, w, h, y, x, sr, sc);
             std::memcpy(dst + (size_t)y * dst_stride + (size_t)x * bpp, src + (size_t)sr * stride + (size_t)sc * bpp, bpp);
         }
+    return JPGE_OK;
+}
+
+int jpge_demosaic_frame(int format, const uint8_t* src, uint32_t w, uint32_t h, size_t stride, uint8_t* dst_rgb8,
+                        size_t dst_stride) {
+    if (!jpge::fmt_bayer(format) || !src || !dst_rgb8 || w < 2 || h < 2) return JPGE_E_ARG;
+    if (!stride) stride = w;
+    if (!dst_stride) dst_stride = (size_t)w * 3;
+    if (stride < w || dst_stride < (size_t)w * 3) return JPGE_E_ARG;
+    const uint32_t phase = jpge::bayer_phase(format);
+    for (uint32_t y = 0; y < h; ++y) {
+        const uint8_t* ra = src + (size_t)jpge::bayer_before(y) * stride;
+        const uint8_t* rm = src + (size_t)y * stride;
+        const uint8_t* rb = src + (size_t)jpge::bayer_after(y, h) * stride;
+        // a column of the 3x3 neighbourhood: V(y - 1) | V(y) << 8 | V(y + 1) << 16
+        auto column = [&](uint32_t x) { return (uint32_t)ra[x] | ((uint32_t)rm[x] << 8) | ((uint32_t)rb[x] << 16); };
+        uint8_t* d = dst_rgb8 + (size_t)y * dst_stride;
+        for (uint32_t x = 0; x < w; ++x) {
+            const uint32_t p = jpge::bayer_rgb(phase, y, x, column(jpge::bayer_before(x)), column(x), column(jpge::bayer_after(x, w)));
+            d[3 * x] = (uint8_t)p;
+            d[3 * x + 1] = (uint8_t)(p >> 8);
+            d[3 * x + 2] = (uint8_t)(p >> 16);
+        }
+    }
     return JPGE_OK;
 }
 

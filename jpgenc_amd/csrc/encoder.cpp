@@ -742,6 +742,9 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     // Y, Cb, Cr samples are 8-bit, and half-size chroma planes are the S420_m mode's planes
     if (fmt_yuv(f.fmt) && (f.maxval != 255 || (fmt_yuv420(f.fmt) && mode_ != 420))) return kErrArg;
     if (gray && f.maxval != 255) return kErrArg;
+    // a Bayer mosaic: bytes as they are, a 2x2 cell at least (a reflected neighbour exists), coded at
+    // full size and as it lies (ds_fmt and orient_fmt above refuse the other settings; one plane)
+    if (fmt_bayer(f.fmt) && (f.maxval != 255 || f.width < 2 || f.height < 2)) return kErrArg;
     // 10-bit layouts: 16-bit words, so an even base and even pitches
     if (fmt_yuv10(f.fmt) && (((uintptr_t)f.rgb | f.stride | f.plane_stride) & 1)) return kErrArg;
     // (v210: 32-bit words, so a base and a pitch that are multiples of 4)

@@ -19,6 +19,7 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     if (ds_ > 1) return kErrArg;       // and are coded at full size (jpge_set_downscale)
     if (orient_) return kErrArg;       // and as they lie (jpge_set_orientation)
     if (fmt_planes(fmt_) != 1 || fmt_gray(fmt_) || fmt_yuv(fmt_)) return kErrArg;  // and interleaved colour (the stripe pointer is one row of pixels)
+    if (fmt_bayer(fmt_)) return kErrArg;  // (a mosaic's stripe would need its neighbours' rows)
     if (d.maxval < 1 || d.maxval > 255) return kErrRange;
     const uint32_t mh_img = (d.height + 15) / 16;
     if (d.mcu_rows == 0 || d.mcu_row0 >= mh_img || d.mcu_rows > mh_img - d.mcu_row0) return kErrArg;

@@ -172,7 +172,7 @@ __device__ __forceinline__ void swap_halves(double& a, double& b) {
 #define JPGE_K1_SHAPE 0
 #endif
 constexpr int kShape = JPGE_K1_SHAPE;
-static_assert(kShape >= kShapeRgb8 && kShape <= kShapeV210, "JPGE_K1_SHAPE");
+static_assert(kShape >= kShapeRgb8 && kShape <= kShapeBayer8, "JPGE_K1_SHAPE");
 // The Y, Cb, Cr shapes (NV12, I420, planar 4:4:4) stage words Y | Cb<<8 | Cr<<16, a 4:2:0
 // layout's chroma sample in each pixel of its 2x2 cell, and read them back without a colour
 // conversion: a sample v is v - 128.  NV12 and I420 run the kFiltS420 instance, which
@@ -181,7 +181,11 @@ static_assert(kShape >= kShapeRgb8 && kShape <= kShapeV210, "JPGE_K1_SHAPE");
 // on its way to a double; nothing else differs.
 // The gray shape stages words that hold Y alone and has the row-8 kernel's one-component
 // instance only: 16 one-block MCUs per tile, the two Y rounds, no chroma rounds.
-constexpr bool kYuv = kShape >= kShapeNv12;
+// The Bayer shape stages the RGB shapes' words R | G<<8 | B<<16, each the bilinear demosaic of a raw
+// byte and its 3x3 neighbourhood ("Bayer loads" below), and has the kExact instances only (maxval is
+// 255), in 4-wave workgroups and frame sets, as the downscaling and the oriented builds.
+constexpr bool kBayer = kShape == kShapeBayer8;
+constexpr bool kYuv = kShape >= kShapeNv12 && !kBayer;
 constexpr bool kGray = kShape == kShapeGray;
 // The 10-bit 4:2:0 shapes (P010, I010) stage words s_y | s_cb<<10 | s_cr<<20 of 10-bit samples s,
 // each the exact fp64 value s / 4 in 8-bit units, and have the !kExact instances only: the
@@ -207,7 +211,7 @@ constexpr bool kPacked422 = kShape == kShapePacked422;
 constexpr bool kPlanes422 = kShape == kShapeNv16 || kShape == kShapeI422;  // chroma loads of their own, row = pixel row
 constexpr bool kPairs = kShape == kShapeNv12 || kShape == kShapeNv16;      // Cb,Cr byte pairs
 constexpr bool kHalfPitch = kShape == kShapeI420 || kShape == kShapeI422;  // chroma pitch (stride + 1) / 2
-constexpr uint32_t kBpp = kShape == kShapeX4 || kShape == kShapeY210 ? 4u : kPacked422 || kTen ? 2u : kShape == kShapePlanar || kYuv ? 1u : 3u;  // bytes per pixel along a row
+constexpr uint32_t kBpp = kShape == kShapeX4 || kShape == kShapeY210 ? 4u : kPacked422 || kTen ? 2u : kShape == kShapePlanar || kYuv || kBayer ? 1u : 3u;  // bytes per pixel along a row
 constexpr uint32_t kRun = 16 * kBpp;  // bytes of a lane's 16-pixel run (of one plane)
 // The downscaling builds (JPGE_K1_DS 2 or 4; FdctArgs::ds) of the RGB8, BGR8, 4-byte and NV12
 // shapes: a staged word holds the rounded means of kDs x kDs source samples, so the lane's run
@@ -506,7 +510,7 @@ __device__ __forceinline__ uint32_t edge_pixel(const uint8_t* rgb, uint64_t stri
 // inside their row, so the range is the last row's end.
 struct RgbRsrc {
     __amdgpu_buffer_rsrc_t p0;
-#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7 && JPGE_K1_SHAPE != 8 && JPGE_K1_SHAPE != 13 && JPGE_K1_SHAPE != 16
+#if JPGE_K1_SHAPE >= 3 && JPGE_K1_SHAPE != 7 && JPGE_K1_SHAPE != 8 && JPGE_K1_SHAPE != 13 && JPGE_K1_SHAPE != 16 && JPGE_K1_SHAPE != 17
     __amdgpu_buffer_rsrc_t p1, p2;  // (NV12, NV16: p2 repeats p1, unused)
 #endif
 };
@@ -621,6 +625,105 @@ __device__ __forceinline__ void load_run(const RgbRsrc& rs, uint32_t off, uint32
     v2 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 32, 0, 0));
     if constexpr (kShape == kShapeX4) v3 = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, off + 48, 0, 0));
 #endif
+}
+
+// ---- Bayer loads (kBayer) ----
+// A lane's run of 16 output pixels on row y, columns xs .. xs + 15, needs raw rows y - 1, y, y + 1 and
+// columns xs - 1 .. xs + 16.  The reflection of jpge.h (row -1 is row 1, row gh is row gh - 2, the
+// columns likewise) is applied to the addresses: the lane loads 16 bytes of each of the three rows
+// and the byte on either side of each, six narrow loads, every one inside the frame's rows.  So the
+// fast path's conditions are the RGB shapes': an aligned source, and the run inside the frame.  The
+// rows above and below are the neighbouring lanes' own rows, from the L1.
+// (ya, ym, yb: the rows' byte offsets; xl, xr: the columns left and right of the run)
+__device__ __forceinline__ void load_bayer(const RgbRsrc& rs, bool ok, uint32_t ya, uint32_t ym, uint32_t yb, uint32_t xs,
+                                           uint32_t xl, uint32_t xr, uint4& v0, uint4& v1, uint4& v2, uint32_t (&h)[6]) {
+    const uint32_t row[3] = {ya, ym, yb};
+    uint4* const v[3] = {&v0, &v1, &v2};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        *v[r] = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rs.p0, ok ? row[r] + xs : kOob, 0, 0));
+        h[2 * r] = __builtin_amdgcn_raw_buffer_load_b8(rs.p0, ok ? row[r] + xl : kOob, 0, 0);
+        h[2 * r + 1] = __builtin_amdgcn_raw_buffer_load_b8(rs.p0, ok ? row[r] + xr : kOob, 0, 0);
+    }
+}
+// z where the mask is 0, y where it is all ones: one v_bfi_b32 (a ternary on a per-lane condition
+// becomes a divergent branch, see unpack_v210)
+__device__ __forceinline__ uint32_t bit_select(uint32_t m, uint32_t y, uint32_t z) { return z ^ (m & (y ^ z)); }
+// The run as 16 staged words.  va, vm, vb: the three rows' 16 bytes; h: the bytes left and right of
+// each.  dy: the row is a B row (bayer_rgb); q: the run's even pixels are G sites (dy ^ the column
+// parity of the R sites), both per lane.  Four pixels at a time, a word of each row:
+//   - the R or B sites are bytes q and 2 + q.  v_perm lifts those two bytes of a word, or of its
+//     left or right neighbours (from the word pair), into 16-bit fields; four such values are
+//     summed with plain 32-bit adds (no carry between the fields: at most 1022) for G and for the
+//     other colour, and the site's own byte is the third.
+//   - the G sites, the other two bytes: v_lerp_u8 is the rounded mean of two words' bytes, all four
+//     at once, of the words shifted a byte either way (the row's colour) and of the rows above and
+//     below (the column's).
+// A word R | G<<8 | B<<16 is then two v_perm; on a B row the sources of the low and the high byte
+// trade places first.  The selectors are per-lane registers, so nothing branches.
+__device__ __forceinline__ void unpack_bayer(const uint4& va, const uint4& vm, const uint4& vb, const uint32_t (&h)[6],
+                                             uint32_t dy, uint32_t q, uint32_t px[16]) {
+    // words -1 .. 4 of each row: the byte on the left is the top byte of word -1, the one on the right the low byte of word 4
+    const uint32_t a[6] = {h[0] << 24, va.x, va.y, va.z, va.w, h[1]};
+    const uint32_t m[6] = {h[2] << 24, vm.x, vm.y, vm.z, vm.w, h[3]};
+    const uint32_t b[6] = {h[4] << 24, vb.x, vb.y, vb.z, vb.w, h[5]};
+    uint32_t mdy = dy ? ~0u : 0u, mq = q ? ~0u : 0u;
+    asm("" : "+v"(mdy), "+v"(mq));
+    const uint32_t q2 = q * 0x00010001u;
+    // bytes q, 2 + q of a word; the bytes left of them (3 + q, 5 + q of the pair previous, word);
+    // the bytes right of them (1 + q, 3 + q of the pair word, next)
+    const uint32_t sel_c = 0x0C020C00u + q2, sel_l = 0x0C050C03u + q2, sel_r = 0x0C030C01u + q2;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t aw = a[w + 1], mw = m[w + 1], bw = b[w + 1];
+        const uint32_t c2 = __builtin_amdgcn_perm(0u, mw, sel_c);
+        const uint32_t g2 = ((__builtin_amdgcn_perm(0u, aw, sel_c) + __builtin_amdgcn_perm(0u, bw, sel_c) +
+                              __builtin_amdgcn_perm(mw, m[w], sel_l) + __builtin_amdgcn_perm(m[w + 2], mw, sel_r) + 0x00020002u) >> 2) & 0x00FF00FFu;
+        const uint32_t d2 = ((__builtin_amdgcn_perm(aw, a[w], sel_l) + __builtin_amdgcn_perm(a[w + 2], aw, sel_r) +
+                              __builtin_amdgcn_perm(bw, b[w], sel_l) + __builtin_amdgcn_perm(b[w + 2], bw, sel_r) + 0x00020002u) >> 2) & 0x00FF00FFu;
+        const uint32_t hh = __builtin_amdgcn_lerp(__builtin_amdgcn_alignbyte(mw, m[w], 3u), __builtin_amdgcn_alignbyte(m[w + 2], mw, 1u), 0x01010101u);
+        const uint32_t vv = __builtin_amdgcn_lerp(aw, bw, 0x01010101u);
+        // the low and the high byte's sources (an R row: own colour, diagonals; row mean, column mean)
+        const uint32_t rlo = bit_select(mdy, d2, c2), rhi = bit_select(mdy, c2, d2);
+        const uint32_t glo = bit_select(mdy, vv, hh), ghi = bit_select(mdy, hh, vv);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            // the R or B site: field k of rlo, g2, rhi
+            const uint32_t t = __builtin_amdgcn_perm(g2, rlo, 0x0C0C0000u | ((4u + 2u * k) << 8) | (2u * k));
+            const uint32_t rb = __builtin_amdgcn_perm(rhi, t, 0x0C000100u | ((4u + 2u * k) << 16));
+            // the G site: byte 2k + 1 - q of glo, the word, ghi
+            const uint32_t bg = 2u * k + 1u - q;
+            const uint32_t u = __builtin_amdgcn_perm(mw, glo, 0x0C0C0000u | ((4u + bg) << 8) | bg);
+            const uint32_t g = __builtin_amdgcn_perm(ghi, u, 0x0C000100u | ((4u + bg) << 16));
+            px[4 * w + 2 * k] = bit_select(mq, g, rb);
+            px[4 * w + 2 * k + 1] = bit_select(mq, rb, g);
+        }
+    }
+}
+// The clamped path of a lane: the run's 16 words written to dst one by one, in a loop that stays
+// rolled.  A coordinate is clamped in the demosaiced frame first (row min(y, gh - 1), column
+// min(xs + i, gw - 1)), and that pixel's neighbours are the reflected ones.  The 3x3 window slides:
+// three byte loads a pixel (a column), by plain pointers, any base and pitch.
+__device__ __forceinline__ void edge_bayer(const uint8_t* base, uint64_t stride, uint32_t gw, uint32_t gh, uint32_t phase,
+                                           uint32_t y, uint32_t xs, uint32_t* dst) {
+    const uint32_t sy = min(y, gh - 1);
+    const uint8_t* ra = base + (uint64_t)bayer_before(sy) * stride;
+    const uint8_t* rm = base + (uint64_t)sy * stride;
+    const uint8_t* rb = base + (uint64_t)bayer_after(sy, gh) * stride;
+    auto column = [&](uint32_t x) { return (uint32_t)ra[x] | ((uint32_t)rm[x] << 8) | ((uint32_t)rb[x] << 16); };
+    uint32_t cx = min(xs, gw - 1);
+    uint32_t l = column(bayer_before(cx)), m = column(cx), r = 0;
+#pragma unroll 1
+    for (uint32_t i = 0; i < 16; ++i) {
+        const uint32_t x = min(xs + i, gw - 1);
+        if (x != cx) {  // one column on (r was column cx + 1, inside the frame)
+            l = m;
+            m = r;
+            cx = x;
+        }
+        r = column(bayer_after(cx, gw));
+        dst[i] = bayer_rgb(phase, sy, cx, l, m, r);
+    }
 }
 
 // ---- downscaling loads (kDs > 1) ----
@@ -831,6 +934,11 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         sel4_ = a.fmt == kFmtUyvy ? kSelUyvy : kSelYuyv;
         asm volatile("" : "+s"(sel4_));
     }
+    uint32_t phase_ = 0;             // Bayer: the CFA phase of the frame's layout (kernels.hpp bayer_phase)
+    if constexpr (kBayer) {
+        phase_ = bayer_phase(a.fmt);
+        asm volatile("" : "+s"(phase_));
+    }
     XfK xf{};  // (the Y, Cb, Cr shapes' !kExact instances)
     if constexpr (kYuv && !kExact) xf = xf_load(a);
     constexpr int kK1Threads = kWaves * 64;
@@ -906,6 +1014,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         cpitch = kPairs ? (uint32_t)stride_ : (uint32_t)((stride_ + 1) / 2);
         lane_coff = (uint32_t)r16 * cpitch + (kPairs ? (uint32_t)c16 : (uint32_t)(c16 >> 1)) * 16;
     }
+    uint32_t hb[6];  // (Bayer: the prefetched bytes left and right of the run's three rows)
     auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * 4;
@@ -920,6 +1029,14 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
             // (ok: r < sh and c0 + 16 <= sw, so the offset is inside the descriptor's range, below 2^32)
             const uint32_t sr = rows_back_ ? sh_ - 1 - r : r, sc = kOrMirror ? sw_ - 16 - c0 : c0;
             load_run(rgb_rs, ok ? sr * (uint32_t)stride_ + sc * kBpp : kOob, kOob, v0, v1, v2, v3);
+            return ok;
+        }
+        if constexpr (kBayer) {
+            // ("Bayer loads" above; ok: every row and column is inside the frame, the offsets below 2^32)
+            const bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
+            const uint32_t st = (uint32_t)stride_;
+            load_bayer(rgb_rs, ok, bayer_before(y) * st, y * st, bayer_after(y, gh_) * st, xs, bayer_before(xs),
+                       bayer_after(xs + 15, gw_), v0, v1, v2, hb);
             return ok;
         }
         bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
@@ -1139,6 +1256,10 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
         if constexpr (kDs > 1) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) px[i] = nx[i];
+        } else if constexpr (kBayer) {
+            // (y's parity is r16's: a tile starts on an even row; xs is even)
+            const uint32_t dy = ((uint32_t)r16 ^ (phase_ >> 1)) & 1u;
+            unpack_bayer(c0, c1, c2, hb, dy, (dy ^ phase_) & 1u, px);
         } else if constexpr (kV210) {
             unpack_v210(c0, c1, c2, c3, (xs >> 4) % 3, px);
         } else if constexpr (kTen) {
@@ -1168,7 +1289,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
                 px[15 - i] = t;
             }
         }
-        if (!cfast) {  // right/bottom edge replication (Image.cpp:498-531) as clamped addressing
+        if (!kBayer && !cfast) {  // right/bottom edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
             if constexpr (kOrTrans)  // (O's coordinates clamped first, then mapped to the source)
                 for (int i = 0; i < 16; ++i) px[i] = or_pixel(min(mrow * 16 + i, gh_ - 1), min(mcol0 * 16 + (uint32_t)lane, gw_ - 1));
@@ -1189,6 +1310,9 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
             uint32_t* dst = &W.rgbx[r16 * kRgbPitch + c16 * 16];
 #pragma unroll
             for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
+            // (Bayer: a lane on the clamped path writes its words over the ones just staged, in a rolled loop)
+            if constexpr (kBayer)
+                if (!cfast) edge_bayer(rgb_, stride_, gw_, gh_, phase_, y, xs, dst);
         }
         wave_order();
         // prefetch the next tile of this wave (into the registers just staged) while
@@ -1319,6 +1443,11 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
         sel4_ = a.fmt == kFmtUyvy ? kSelUyvy : kSelYuyv;
         asm volatile("" : "+s"(sel4_));
     }
+    uint32_t phase_ = 0;             // Bayer: the CFA phase of the frame's layout (kernels.hpp bayer_phase)
+    if constexpr (kBayer) {
+        phase_ = bayer_phase(a.fmt);
+        asm volatile("" : "+s"(phase_));
+    }
     XfK xf{};  // (the Y, Cb, Cr shapes' !kExact instances)
     if constexpr (kYuv && !kExact) xf = xf_load(a);
     constexpr int kK1Threads = kWaves * 64;
@@ -1370,6 +1499,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
         cpitch = kTenHi ? (uint32_t)stride_ : (uint32_t)(2 * ((stride_ + 3) / 4));
         lane_coff = (uint32_t)r8 * cpitch + (uint32_t)c8 * kCellRun;
     }
+    uint32_t hb[6];  // (Bayer: the prefetched bytes left and right of the run's three rows)
     auto fast_load = [&](uint32_t k, uint4& v0, uint4& v1, uint4& v2, uint4& v3) -> bool {
         const uint32_t t = tb_p + k;
         const uint32_t mrow = t / tiles_per_row, mcol0 = (t % tiles_per_row) * kMcus;
@@ -1378,6 +1508,13 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
             const bool ok = k < n_p && or_aligned && y < gh_ && xs + 16 <= gw_;
             const uint32_t sr = rows_back_ ? sh_ - 1 - y : y, sc = kOrMirror ? sw_ - 16 - xs : xs;
             load_run(rgb_rs, ok ? sr * (uint32_t)stride_ + sc * kBpp : kOob, kOob, v0, v1, v2, v3);
+            return ok;
+        }
+        if constexpr (kBayer) {  // (as in fdct_kernel)
+            const bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
+            const uint32_t st = (uint32_t)stride_;
+            load_bayer(rgb_rs, ok, bayer_before(y) * st, y * st, bayer_after(y, gh_) * st, xs, bayer_before(xs),
+                       bayer_after(xs + 15, gw_), v0, v1, v2, hb);
             return ok;
         }
         bool ok = k < n_p && aligned && y < gh_ && xs + 16 <= gw_;
@@ -1470,6 +1607,9 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
             for (int i = 0; i < 16; ++i) px[i] = nx[i];
         } else if constexpr (kGray) {
             unpack_gray(c0, px);
+        } else if constexpr (kBayer) {
+            const uint32_t dy = ((uint32_t)r8 ^ (phase_ >> 1)) & 1u;  // (as in fdct_kernel)
+            unpack_bayer(c0, c1, c2, hb, dy, (dy ^ phase_) & 1u, px);
         } else if constexpr (kV210) {
             unpack_v210(c0, c1, c2, c3, (xs >> 4) % 3, px);
         } else if constexpr (kTen) {
@@ -1499,7 +1639,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
                 px[15 - i] = t;
             }
         }
-        if (!cfast) {  // edge replication (Image.cpp:498-531) as clamped addressing
+        if (!kBayer && !cfast) {  // edge replication (Image.cpp:498-531) as clamped addressing
             const uint32_t sy = min(y, gh_ - 1);
             if constexpr (kOrient != 0)  // (O's coordinates clamped first, then mapped to the source)
                 for (int i = 0; i < 16; ++i) px[i] = or_pixel(sy, min(xs + i, gw_ - 1));
@@ -1513,6 +1653,8 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
         uint32_t* dst = &W.rgbx[r8 * kRgbPitch444 + c8 * 16];
 #pragma unroll
         for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
+        if constexpr (kBayer)  // (as in fdct_kernel)
+            if (!cfast) edge_bayer(rgb_, stride_, gw_, gh_, phase_, y, xs, dst);
         wave_order();
         if constexpr (kDs > 1) {
             cfast = fast_load_ds(kn, nx);
@@ -1624,6 +1766,9 @@ static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, h
         if (ex) return hipErrorInvalidValue;
         if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+    } else if constexpr (kBayer) {
+        // (the Bayer build has the exact colour path's 4-wave workgroup only: maxval is 255)
+        return !ex ? hipErrorInvalidValue : launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     } else {
         // (the downscaling and the oriented builds have the 4-wave workgroup only: k1_whole_cu is false for them)
         if constexpr (kDs == 1 && kOrient == 0) {
@@ -1647,6 +1792,9 @@ static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hi
         if (ex) return hipErrorInvalidValue;
         if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
+    } else if constexpr (kBayer) {
+        // (the Bayer build has the exact colour path's 4-wave workgroup only: maxval is 255)
+        return !ex ? hipErrorInvalidValue : launch_timed(t, fdct_kernel<true, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     } else {
         // (the downscaling and the oriented builds have the 4-wave workgroup only: k1_whole_cu is false for them)
         if constexpr (kDs == 1 && kOrient == 0) {
@@ -1698,12 +1846,12 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
 
 #if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1 || JPGE_K1_ORIENT != 0
 // this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
-// _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210 / _v210; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...;
+// _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210 / _v210 / _bayer8; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...;
 // the oriented builds: launch_fdct_rgb8_o1 .. _o4, _bgr8_o1, ...)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
-#if JPGE_K1_SHAPE >= 11
+#if JPGE_K1_SHAPE >= 11 && JPGE_K1_SHAPE != 17
 // the 10-bit shapes also have the lone frame's instance (launch_fdct_p010_one / _i010_one / _y210_one / ...), as the RGB8 shape has
 #define JPGE_K1_CAT_(a, b) a##b
 #define JPGE_K1_CAT(a, b) JPGE_K1_CAT_(a, b)
@@ -1734,6 +1882,7 @@ hipError_t launch_fdct_p210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, 
 hipError_t launch_fdct_i210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_v210(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_v210_one(const FrameSet<FdctArgs, 1>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_bayer8(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 // the downscaling builds (FdctArgs::ds 2, 4) of the shapes that have them
 hipError_t launch_fdct_rgb8_d2(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 hipError_t launch_fdct_rgb8_d4(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
@@ -1767,6 +1916,10 @@ uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs, uint32_t
     return wgs < cap ? wgs : cap;
 }
 
+// fdct_grid's last argument for a frame: non-zero rules the whole-CU shape out, for an oriented
+// frame and for a Bayer one (both builds have the 4-wave workgroups only)
+static uint32_t k1_small(const FdctArgs& a) { return fmt_bayer(a.fmt) ? 1u : a.orient; }
+
 // A set of frames of one geometry, colour path and workgroup shape (one launch).
 template <int kN>
 static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s, const KTimer* t) {
@@ -1781,6 +1934,9 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         if (!fmt_valid(m.fmt) || m.g.height == 0 || ((fmt_yuv(m.fmt) || fmt_gray(m.fmt)) && m.maxval != 255) ||
             fmt_gray(m.fmt) != m.g.gray())
             return hipErrorInvalidValue;
+        // (a Bayer frame: a 2x2 cell at least, so that a reflected neighbour exists; one plane; the
+        // exact colour path.  The members of a set may differ in CFA phase: each reads its own.)
+        if (fmt_bayer(m.fmt) && (m.g.width < 2 || m.g.height < 2 || m.maxval != 255 || m.plane_stride)) return hipErrorInvalidValue;
         static_assert(kK1OffsetBound == kOob, "the host's bound is the kernel's out-of-range offset");
         // a downscaled frame: g is the frame of ceil(src / ds) pixels; the offsets span the source
         Geometry src = m.g;
@@ -1812,7 +1968,7 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         if (m.fmt == kFmtV210 && ((((uintptr_t)m.rgb | m.stride) & 3) || m.plane_stride)) return hipErrorInvalidValue;
         if (std::memcmp(&m.g, &a.g, sizeof(Geometry)) != 0 || (m.maxval == 255) != (a.maxval == 255) ||
             fmt_shape(m.fmt) != fmt_shape(a.fmt) || (m.xf_on != 0) != (a.xf_on != 0) ||
-            m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs, m.ds, m.orient))
+            m.solo != a.solo || fs.wg0[f + 1] - fs.wg0[f] != fdct_grid(m.g, m.solo, m.wgs, m.ds, k1_small(m)))
             return hipErrorInvalidValue;
     }
     const uint32_t grid = fs.wg0[fs.n];
@@ -1865,17 +2021,18 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         case kShapeP210: return launch_fdct_p210(w, grid, s, t);
         case kShapeI210: return launch_fdct_i210(w, grid, s, t);
         case kShapeV210: return launch_fdct_v210(w, grid, s, t);
+        case kShapeBayer8: return launch_fdct_bayer8(w, grid, s, t);
         default: return launch_fdct_planar(w, grid, s, t);
     }
 }
 
 hipError_t launch_fdct(const FdctArgs& a, hipStream_t s, const KTimer* t) {
-    return launch_fdct_fs(frame_set<1>(&a, 1, fdct_grid(a.g, a.solo, a.wgs, a.ds, a.orient)), s, t);
+    return launch_fdct_fs(frame_set<1>(&a, 1, fdct_grid(a.g, a.solo, a.wgs, a.ds, k1_small(a))), s, t);
 }
 
 hipError_t launch_fdct_set(const FdctArgs* a, int n, hipStream_t s, const KTimer* t) {
     if (n < 1 || n > kMaxSet) return hipErrorInvalidValue;
-    return launch_fdct_fs(frame_set(a, n, fdct_grid(a[0].g, a[0].solo, a[0].wgs, a[0].ds, a[0].orient)), s, t);
+    return launch_fdct_fs(frame_set(a, n, fdct_grid(a[0].g, a[0].solo, a[0].wgs, a[0].ds, k1_small(a[0]))), s, t);
 }
 #endif  // JPGE_K1_SHAPE == 0
 

@@ -81,8 +81,37 @@ constexpr int kFmtV210 = 48;
 // one plane of 8-bit luminance samples (a sample v is the fp64 value v - 128, as a Y sample
 // above): a one-component stream, Geometry::gray(), whatever the subsampling mode
 constexpr int kFmtGray8 = 8;
+// 8-bit Bayer mosaics (camera raw, white balance and gamma applied in the camera): one plane of one
+// byte per pixel, the name the colours of the 2x2 cell at rows 0-1, columns 0-1, read row by row.
+// The frame codes as the RGB8 frame of its bilinear demosaic (jpge.h; bayer_rgb below), built in
+// K1's tile staging.  code - kFmtBayerRggb8 is the phase: bit 0 the column parity of the R sites,
+// bit 1 their row parity.
+constexpr int kFmtBayerRggb8 = 10, kFmtBayerGrbg8 = 11, kFmtBayerGbrg8 = 12, kFmtBayerBggr8 = 13;
+JPGE_HD inline bool fmt_bayer(int fmt) { return fmt >= kFmtBayerRggb8 && fmt <= kFmtBayerBggr8; }
+JPGE_HD inline uint32_t bayer_phase(int fmt) { return (uint32_t)(fmt - kFmtBayerRggb8); }
+// a neighbour's coordinate, reflected without repeating the edge (n >= 2): -1 is 1, n is n - 2
+JPGE_HD inline uint32_t bayer_before(uint32_t i) { return i ? i - 1 : 1u; }
+JPGE_HD inline uint32_t bayer_after(uint32_t i, uint32_t n) { return i + 1 < n ? i + 1 : n - 2; }
+// R | G << 8 | B << 16 of site (y, x) from its 3x3 neighbourhood: l, m, r are columns x - 1, x,
+// x + 1 (reflected), each V(y - 1) | V(y) << 8 | V(y + 1) << 16.  The rule of jpge.h in integers;
+// jpge_demosaic_frame and K1's byte path both call it.
+JPGE_HD inline uint32_t bayer_rgb(uint32_t phase, uint32_t y, uint32_t x, uint32_t l, uint32_t m, uint32_t r) {
+    const uint32_t dy = (y ^ (phase >> 1)) & 1, dx = (x ^ phase) & 1;  // (0, 0): an R site; (1, 1): a B site
+    const uint32_t lm = (l >> 8) & 0xFF, rm = (r >> 8) & 0xFF;
+    uint32_t lo, mid, hi;  // on an R row: R, G, B; on a B row lo and hi trade places
+    if (dx == dy) {  // R or B: its own colour, G of the four beside it, the other colour of the diagonals
+        lo = (m >> 8) & 0xFF;
+        mid = ((m & 0xFF) + (m >> 16) + lm + rm + 2) >> 2;
+        hi = ((l & 0xFF) + (l >> 16) + (r & 0xFF) + (r >> 16) + 2) >> 2;
+    } else {  // G: its row's colour left and right, its column's colour above and below
+        lo = (lm + rm + 1) >> 1;
+        mid = (m >> 8) & 0xFF;
+        hi = ((m & 0xFF) + (m >> 16) + 1) >> 1;
+    }
+    return dy ? hi | (mid << 8) | (lo << 16) : lo | (mid << 8) | (hi << 16);
+}
 JPGE_HD inline bool fmt_valid(int fmt) {
-    return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar) ||
+    return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || fmt_bayer(fmt) || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar) ||
            (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt == kFmtP010 || fmt == kFmtI010 ||
            (fmt >= kFmtY210 && fmt <= kFmtI210) || fmt == kFmtV210;
 }
@@ -110,14 +139,15 @@ constexpr int kShapeY210 = 13;   // the run's 64 bytes (8 groups of four words):
 constexpr int kShapeP210 = 14;   // the P010 shape's four loads, the Cb,Cr row that of the pixels
 constexpr int kShapeI210 = 15;   // the I010 shape's four loads, the chroma rows those of the pixels
 constexpr int kShapeV210 = 16;   // the three or four 16-byte groups that hold the run: four b128 loads, a per-lane phase
+constexpr int kShapeBayer8 = 17; // 16 raw bytes of rows y - 1, y, y + 1 and the six bytes beside them: three b128 and six byte loads
 JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt == kFmtV210 ? kShapeV210 : fmt == kFmtY210 ? kShapeY210 : fmt == kFmtP210 ? kShapeP210 : fmt == kFmtI210 ? kShapeI210 : fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
+    return fmt_bayer(fmt) ? kShapeBayer8 : fmt == kFmtV210 ? kShapeV210 : fmt == kFmtY210 ? kShapeY210 : fmt == kFmtP210 ? kShapeP210 : fmt == kFmtI210 ? kShapeI210 : fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
          : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
 }
 // bytes per pixel within a row (planar: of one plane), and planes
 // (v210: 0, a row is no whole number of bytes per pixel; fmt_row_bytes has its rows)
 JPGE_HD inline uint64_t v210_row_bytes(uint32_t width) { return 16 * (((uint64_t)width + 5) / 6); }
-JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtV210 ? 0u : fmt_packed422(fmt) || fmt_yuv10(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
+JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtV210 ? 0u : fmt_packed422(fmt) || fmt_yuv10(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) || fmt_bayer(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
 JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) || fmt == kFmtY210 || fmt == kFmtV210 ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 || fmt == kFmtP010 || fmt == kFmtP210 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
 // The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
 // that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs; NV16 likewise; the packed
@@ -212,6 +242,8 @@ struct FdctArgs {
 static_assert(sizeof(FdctArgs) == 336 && offsetof(FdctArgs, q) == 64 && offsetof(FdctArgs, xf) == 272,
               "the downscale fields sit in padding: the argument block's layout is unchanged");
 static_assert(offsetof(FdctArgs, ds) == 56 && offsetof(FdctArgs, orient) == 60, "the orientation sits in padding too");
+// (The block has no padding left.  A Bayer frame's CFA phase needs no field: it is bayer_phase(fmt),
+// which each member of a frame set reads from its own block, as the 4-byte shape reads its channel order.)
 
 // Box downscale by 2 or 4 inside K1 (jpge.h jpge_set_downscale): the interleaved RGB layouts in
 // every subsampling mode, and NV12 (whose Cb,Cr plane is averaged in its own domain).

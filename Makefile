@@ -21,7 +21,9 @@ HOST_OBJS := $(addprefix $(BUILD)/,$(HOST_SRCS:.cpp=.o))
 K1_DS_SRCS := fdct_rgb8_d2.hip fdct_rgb8_d4.hip fdct_bgr8_d2.hip fdct_bgr8_d4.hip fdct_x4_d2.hip fdct_x4_d4.hip fdct_nv12_d2.hip fdct_nv12_d4.hip
 # (fdct_*_o1 .. _o4: the shapes' oriented builds, jpge_set_orientation)
 K1_OR_SRCS := $(foreach s,rgb8 bgr8 x4,$(foreach c,1 2 3 4,fdct_$(s)_o$(c).hip))
-DEV_SRCS  := fdct.hip fdct_bgr8.hip fdct_x4.hip fdct_planar.hip fdct_nv12.hip fdct_i420.hip fdct_yuv444.hip fdct_gray.hip fdct_packed422.hip fdct_nv16.hip fdct_i422.hip fdct_p010.hip fdct_i010.hip fdct_y210.hip fdct_p210.hip fdct_i210.hip fdct_v210.hip fdct_bayer8.hip $(K1_DS_SRCS) $(K1_OR_SRCS) stats.hip entropy.hip planes.hip concat.hip
+# (fdct_*_lut: the shapes' builds that map each staged pixel through the context's channel tables, jpge_set_channel_lut)
+K1_LUT_SRCS := fdct_rgb8_lut.hip fdct_bgr8_lut.hip fdct_x4_lut.hip fdct_bayer8_lut.hip
+DEV_SRCS  := fdct.hip fdct_bgr8.hip fdct_x4.hip fdct_planar.hip fdct_nv12.hip fdct_i420.hip fdct_yuv444.hip fdct_gray.hip fdct_packed422.hip fdct_nv16.hip fdct_i422.hip fdct_p010.hip fdct_i010.hip fdct_y210.hip fdct_p210.hip fdct_i210.hip fdct_v210.hip fdct_bayer8.hip $(K1_DS_SRCS) $(K1_OR_SRCS) $(K1_LUT_SRCS) stats.hip entropy.hip planes.hip concat.hip
 DEV_OBJS  := $(addprefix $(BUILD)/,$(DEV_SRCS:.hip=.o))
 DIAG_OBJS := $(addprefix $(BUILD)/diag/,$(DEV_SRCS:.hip=.o))
 HEADERS   := $(wildcard $(SRC)/*.hpp) include/jpge.h
@@ -35,7 +37,7 @@ YUVXF_TEST  := tests/cpp/bin/test_yuvxf
 all: $(LIBDIR)/libjpge.so $(BINDIR)/jpgenc $(FACADE_TEST) $(HUFF_TEST) $(QUANT_TEST) $(EXIT_TEST) $(HUFFSPEC_TEST) $(YUVXF_TEST) oracle
 
 # (fdct_*.hip: fdct.hip built per input load shape)
-K1_SHAPES := fdct_bgr8.o fdct_x4.o fdct_planar.o fdct_nv12.o fdct_i420.o fdct_yuv444.o fdct_gray.o fdct_packed422.o fdct_nv16.o fdct_i422.o fdct_p010.o fdct_i010.o fdct_y210.o fdct_p210.o fdct_i210.o fdct_v210.o fdct_bayer8.o $(K1_DS_SRCS:.hip=.o) $(K1_OR_SRCS:.hip=.o)
+K1_SHAPES := fdct_bgr8.o fdct_x4.o fdct_planar.o fdct_nv12.o fdct_i420.o fdct_yuv444.o fdct_gray.o fdct_packed422.o fdct_nv16.o fdct_i422.o fdct_p010.o fdct_i010.o fdct_y210.o fdct_p210.o fdct_i210.o fdct_v210.o fdct_bayer8.o $(K1_DS_SRCS:.hip=.o) $(K1_OR_SRCS:.hip=.o) $(K1_LUT_SRCS:.hip=.o)
 $(addprefix $(BUILD)/,$(K1_SHAPES)) $(addprefix $(BUILD)/diag/,$(K1_SHAPES)): $(SRC)/fdct.hip
 
 $(BUILD)/%.o: $(SRC)/%.hip $(HEADERS)

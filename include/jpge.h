@@ -313,8 +313,9 @@ int jpge_set_subsampling(jpge_ctx* ctx, int mode);
  * maxval other than 255, a plane_stride other than 0, a downscale factor above 1, an orientation
  * other than JPGE_ORIENT_NONE, jpge_stripe_transform and jpge_group_encode_striped.
  * jpge_encode_planes and the plane stages ignore the layout.  The fast path needs the pointer and
- * the stride 16-byte aligned.  Not built: other demosaic filters, deeper or packed raw, white
- * balance, colour matrix and gamma. */
+ * the stride 16-byte aligned.  Not built: other demosaic filters, deeper or packed raw and a colour
+ * matrix; white balance gains and a gamma curve are jpge_set_channel_lut's
+ * tables, applied to the demosaiced pixel. */
 #define JPGE_FMT_BAYER_RGGB8 10
 #define JPGE_FMT_BAYER_GRBG8 11
 #define JPGE_FMT_BAYER_GBRG8 12
@@ -545,6 +546,49 @@ int jpge_oriented_size(uint32_t width, uint32_t height, int orientation, uint32_
  * zero dimension, a NULL pointer or a stride below a row's bytes. */
 int jpge_orient_frame(int format, const uint8_t* src, uint32_t width, uint32_t height, size_t stride, int orientation,
                       uint8_t* dst, size_t dst_stride);
+
+/* Per-channel lookup tables (an addition): a tone curve applied inside the transform kernel as it
+ * stages a tile -- black level, per-channel gain (white balance), gamma or an sRGB curve, contrast
+ * stretch, inversion -- with no pass over the surface in front of the encode.
+ *
+ * lut is 768 bytes T: T[0..255] for R, T[256..511] for G, T[512..767] for B.  Take a frame F in
+ * layout L and let D(F) be its RGB8 frame: the pixels rearranged for JPGE_FMT_RGB8, _BGR8, _RGBA8
+ * and _BGRA8, and jpge_demosaic_frame(F) for the four Bayer layouts.  With tables set, F codes as
+ * the RGB8 frame M with
+ *     M[y][x][c] = T[256 * c + D[y][x][c]]        c = 0 (R), 1 (G), 2 (B).
+ * The table is chosen by colour, not by byte position (BGR8: the byte at offset 0 goes through
+ * the B table); alpha is ignored, as without tables; a Bayer frame's tables act on the demosaiced
+ * pixel (after the bilinear rule), not on the raw byte.  All of it is integer: the .jpg is, byte
+ * for byte, that of M coded as JPGE_FMT_RGB8 with no tables on the same context, under every other
+ * setting (quality tables, the six subsampling modes, restart interval, Huffman mode, lanes and
+ * frame sets, jpge_encode_batch, jpge_group_encode_batch); jpge_fdct_quant and jpge_symbol_stats
+ * return M's coefficients and histograms.  Padding to whole MCUs replicates M's edge pixels (the
+ * map is per pixel, so it commutes with the clamp).  The identity tables give the bytes of a
+ * context without tables; a context that never calls the setter launches the kernels it launched
+ * before this entry existed.
+ *
+ * jpge_set_channel_lut: NULL switches the tables off (the default).  The 768 bytes are copied, to
+ * the host and to the device (on a stream of the context's own, awaited), so the caller's buffer
+ * is free on return.  The setting applies to jpge_encode_rgb8, jpge_encode_batch, jpge_fdct_quant,
+ * jpge_symbol_stats, jpge_encode_file(s) and, on a group member's context, jpge_group_encode_batch.
+ * With tables set these return JPGE_E_ARG before anything is queued (a batch or a file list: the
+ * frame's status; the context stays usable): a layout other than RGB8, BGR8, RGBA8, BGRA8 and the
+ * four Bayer ones; maxval other than 255 (a PPM file's too); a downscale factor above 1; an
+ * orientation other than JPGE_ORIENT_NONE; jpge_stripe_transform and jpge_group_encode_striped.
+ * jpge_encode_planes and the plane stages ignore the setting.  Not built: planar RGB, GRAY8 and
+ * the Y, Cb, Cr layouts, a 3x3 colour matrix, tables deeper than 8 bits.
+ * jpge_get_channel_lut: *on is 0 or 1; lut (may be NULL) receives the bytes last set.
+ * Speed: about the transform kernel's time without tables. */
+int jpge_set_channel_lut(jpge_ctx* ctx, const uint8_t lut[768]);
+int jpge_get_channel_lut(jpge_ctx* ctx, int* on, uint8_t lut[768]);
+/* The rule above in plain C++, host only, for the four interleaved layouts: src (width x height
+ * in `format`, row pitch stride, 0 = dense) to dst in the same layout (dst_stride likewise; dst
+ * may be src).  A 4-byte layout's fourth byte is copied.  Bytes of dst outside its rows' pixels
+ * are not written.  JPGE_E_ARG: another layout, a zero dimension, a NULL pointer, or a stride
+ * below a row's bytes; a refused call writes nothing.  It has no Bayer case: compose it with
+ * jpge_demosaic_frame. */
+int jpge_lut_frame(int format, const uint8_t* src, uint32_t width, uint32_t height, size_t stride, const uint8_t lut[768],
+                   uint8_t* dst, size_t dst_stride);
 
 /* Worst-case .jpg size for a frame, in any subsampling mode (header + 2x
  * worst-case entropy + RST markers + EOI). */

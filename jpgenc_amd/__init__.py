@@ -82,6 +82,7 @@ EXPORTS = (
     "jpge_strerror", "jpge_version", "jpge_device_count", "jpge_open", "jpge_open_ex", "jpge_close", "jpge_set_timing",
     "jpge_get_timing", "jpge_reset_timing", "jpge_get_lanes", "jpge_set_restart_interval", "jpge_set_subsampling",
     "jpge_set_input_format", "jpge_get_input_format", "jpge_input_format_info", "jpge_demosaic_frame",
+    "jpge_set_channel_lut", "jpge_get_channel_lut", "jpge_lut_frame",
     "jpge_v210_row_bytes", "jpge_v210_unpack",
     "jpge_set_huffman", "jpge_get_huffman", "jpge_standard_huffman",
     "jpge_set_yuv_transform", "jpge_get_yuv_transform", "jpge_yuv_preset",
@@ -242,6 +243,9 @@ def lib() -> ctypes.CDLL:
         L.jpge_oriented_size.argtypes = [u32, u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
         L.jpge_orient_frame.argtypes = [i32, vp, u32, u32, sz, i32, vp, sz]
         L.jpge_demosaic_frame.argtypes = [i32, vp, u32, u32, sz, vp, sz]
+        L.jpge_set_channel_lut.argtypes = [vp, vp]
+        L.jpge_get_channel_lut.argtypes = [vp, ctypes.POINTER(i32), vp]
+        L.jpge_lut_frame.argtypes = [i32, vp, u32, u32, sz, vp, vp, sz]
         L.jpge_device_count.argtypes = [ctypes.POINTER(i32)]
         L.jpge_max_jpeg_bytes.restype = sz
         L.jpge_max_jpeg_bytes.argtypes = [u32, u32]
@@ -905,6 +909,31 @@ def demosaic_frame(a, fmt: int):
     return out
 
 
+def _channel_lut(lut) -> np.ndarray:
+    """The (3, 256) uint8 tables (R, G, B) of a set_channel_lut / lut_frame argument: a (3, 256)
+    uint8 array, or a (256,) one used for all three channels."""
+    t = np.asarray(lut)
+    if t.dtype != np.uint8 or t.shape not in ((3, 256), (256,)):
+        raise ValueError(f"lookup tables of shape {t.shape} and type {t.dtype}: a (3, 256) uint8 array "
+                         "(the R, G and B tables) or a (256,) one for all three channels")
+    return np.ascontiguousarray(np.broadcast_to(t, (3, 256)))
+
+
+def lut_frame(a, fmt: int, lut):
+    """The frame an encode with Encoder.set_channel_lut(lut) codes for the (H, W, 3) or (H, W, 4)
+    uint8 frame `a` in layout `fmt` (RGB8, BGR8, RGBA8, BGRA8), in the same layout: every R, G, B
+    byte through its colour's table, alpha copied (jpge_lut_frame, on the host).  A Bayer frame:
+    lut_frame(demosaic_frame(a, fmt), JPGE_FMT_RGB8, lut)."""
+    t = _channel_lut(lut)
+    a = np.ascontiguousarray(a)
+    if a.ndim != 3 or a.dtype != np.uint8 or a.shape[2] not in (3, 4) or a.size == 0:
+        raise ValueError(f"frame of shape {a.shape} and type {a.dtype}: a non-empty (H, W, 3) or (H, W, 4) uint8 array")
+    h, w, c = a.shape
+    out = np.zeros_like(a)
+    _check(lib().jpge_lut_frame(int(fmt), _p(a), w, h, w * c, _p(t), _p(out), w * c), "lut_frame")
+    return out
+
+
 def device_count() -> int:
     n = ctypes.c_int(0)
     lib().jpge_device_count(ctypes.byref(n))
@@ -1073,6 +1102,23 @@ class Encoder:
         o = ctypes.c_int32()
         _check(lib().jpge_get_orientation(self._ctx, ctypes.byref(o)), "get_orientation")
         return o.value
+
+    def set_channel_lut(self, lut) -> None:
+        """Per-channel lookup tables of the following encodes (the calls set_downscale applies
+        to): None (off, the default), a (3, 256) uint8 array (the R, G and B tables) or a (256,)
+        one used for all three channels.  Every pixel is mapped inside the transform kernel: the
+        bytes are those of encoding lut_frame(frame, fmt, lut) (a Bayer mosaic: of its
+        demosaic_frame) as RGB8.  RGB8, BGR8, RGBA8, BGRA8 and Bayer input of maxval 255; other
+        layouts, a downscale factor above 1, an orientation and the stripe phases fail with
+        JPGE_E_ARG while tables are set.  encode_tensor honours the setting."""
+        t = None if lut is None else _channel_lut(lut)
+        _check(lib().jpge_set_channel_lut(self._ctx, None if t is None else _p(t)), "set_channel_lut")
+
+    def channel_lut(self):
+        """The tables in force: a (3, 256) uint8 array, or None when they are off."""
+        on, t = ctypes.c_int32(), np.zeros((3, 256), np.uint8)
+        _check(lib().jpge_get_channel_lut(self._ctx, ctypes.byref(on), _p(t)), "get_channel_lut")
+        return t if on.value else None
 
     def _cap(self, w: int, h: int) -> int:
         # the output bound of a w x h source: the coded frame's (oriented_size)
@@ -1619,6 +1665,15 @@ class Group:
             _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
             _check(lib().jpge_set_orientation(c, int(o)), "set_orientation")
         self._orient = int(o)
+
+    def set_channel_lut(self, lut) -> None:
+        """Per-channel lookup tables of every member's context (Encoder.set_channel_lut): for
+        encode_batch; encode_striped needs them off."""
+        t = None if lut is None else _channel_lut(lut)
+        for m in range(self.size()[0]):
+            c = ctypes.c_void_p()
+            _check(lib().jpge_group_context(self._g, m, ctypes.byref(c)), "group_context")
+            _check(lib().jpge_set_channel_lut(c, None if t is None else _p(t)), "set_channel_lut")
 
     def encode_batch(self, frames: list[np.ndarray], quality: int = 50, maxval: int = 255) -> list[bytes]:
         """Config 4: frame i on member i mod N."""

@@ -180,7 +180,7 @@ const char* jpge_strerror(int s) {
     }
 }
 
-int jpge_version(void) { return 107; }
+int jpge_version(void) { return 108; }
 
 int jpge_device_count(int* n) {
     if (!n) return JPGE_E_ARG;
@@ -448,6 +448,40 @@ int jpge_demosaic_frame(int format, const uint8_t* src, uint32_t w, uint32_t h, 
             d[3 * x] = (uint8_t)p;
             d[3 * x + 1] = (uint8_t)(p >> 8);
             d[3 * x + 2] = (uint8_t)(p >> 16);
+        }
+    }
+    return JPGE_OK;
+}
+
+int jpge_set_channel_lut(jpge_ctx* ctx, const uint8_t* lut) {
+    CtxUse use(ctx);
+    if (!use) return JPGE_E_ARG;
+    return ctx->enc->set_channel_lut(lut);
+}
+
+int jpge_get_channel_lut(jpge_ctx* ctx, int* on, uint8_t* lut) {
+    CtxUse use(ctx);
+    if (!use || !on) return JPGE_E_ARG;
+    ctx->enc->channel_lut(on, lut);
+    return JPGE_OK;
+}
+
+int jpge_lut_frame(int format, const uint8_t* src, uint32_t w, uint32_t h, size_t stride, const uint8_t* lut, uint8_t* dst,
+                   size_t dst_stride) {
+    if (!jpge::orient_fmt(format) || !src || !dst || !lut || !w || !h) return JPGE_E_ARG;  // (the four interleaved layouts)
+    const size_t bpp = jpge::fmt_bpp(format), row = bpp * w;
+    if (!stride) stride = row;
+    if (!dst_stride) dst_stride = row;
+    if (stride < row || dst_stride < row) return JPGE_E_ARG;
+    // the table of the byte at offset k of a pixel: chosen by colour (BGR8, BGRA8: offset 0 is B)
+    const bool bgr = format == JPGE_FMT_BGR8 || format == JPGE_FMT_BGRA8;
+    const uint8_t* const t[3] = {lut + (bgr ? 512 : 0), lut + 256, lut + (bgr ? 0 : 512)};
+    for (uint32_t y = 0; y < h; ++y) {
+        const uint8_t* s = src + (size_t)y * stride;
+        uint8_t* d = dst + (size_t)y * dst_stride;
+        for (uint32_t x = 0; x < w; ++x, s += bpp, d += bpp) {
+            for (int k = 0; k < 3; ++k) d[k] = t[k][s[k]];
+            if (bpp == 4) d[3] = s[3];
         }
     }
     return JPGE_OK;

@@ -15,7 +15,11 @@
 //   --orient none|flip-h|rot180|flip-v|transpose|rot90|transverse|rot270
 //                                  code the image flipped, rotated (rot90: clockwise) or
 //                                  transposed (jpge_set_orientation; not with --gpus /
-//                                  --devices, nor with --downscale 2|4).
+//                                  --devices, nor with --downscale 2|4);
+//   --lut FILE                     map every sample through per-channel lookup tables: FILE holds
+//                                  exactly 768 raw bytes, the R, G and B tables of 256 entries
+//                                  (jpge_set_channel_lut; a PPM of maxval 255; not with --gpus /
+//                                  --devices, --downscale 2|4 nor an --orient other than none).
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -63,6 +67,7 @@ int main(int argc, char* argv[]) {
     int huffman = JPGE_HUFF_OPTIMAL;
     int downscale = 1;
     int orient = JPGE_ORIENT_NONE;
+    std::vector<uint8_t> lut;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "-q") && i + 1 < argc) {
             quality = std::atoi(argv[++i]);
@@ -101,6 +106,13 @@ int main(int argc, char* argv[]) {
                 std::cerr << "jpgenc: --orient takes none, flip-h, rot180, flip-v, transpose, rot90, transverse or rot270" << std::endl;
                 return 1;
             }
+        } else if (!std::strcmp(argv[i], "--lut") && i + 1 < argc) {
+            std::ifstream f(argv[++i], std::ios::binary);
+            if (f.is_open()) lut.assign((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+            if (lut.size() != 768) {
+                std::cerr << "jpgenc: --lut takes a file of exactly 768 bytes (the R, G and B tables)" << std::endl;
+                return 1;
+            }
         } else {
             pos.emplace_back(argv[i]);
         }
@@ -115,6 +127,7 @@ int main(int argc, char* argv[]) {
             if (huffman != JPGE_HUFF_OPTIMAL) throw std::runtime_error("--huffman standard: not for striped encodes");
             if (downscale != 1) throw std::runtime_error("--downscale: not for striped encodes");
             if (orient != JPGE_ORIENT_NONE) throw std::runtime_error("--orient: not for striped encodes");
+            if (!lut.empty()) throw std::runtime_error("--lut: not for striped encodes");
             return striped(devs, pos[0], jpg, quality, restart);
         }
         auto img = jpge::loadPPM(pos[0]);
@@ -122,6 +135,7 @@ int main(int argc, char* argv[]) {
         if (huffman) jpge::detail::check(jpge_set_huffman(jpge::default_context(), huffman, nullptr), "huffman");
         if (downscale != 1) jpge::detail::check(jpge_set_downscale(jpge::default_context(), downscale), "downscale");
         if (orient != JPGE_ORIENT_NONE) jpge::detail::check(jpge_set_orientation(jpge::default_context(), orient), "orient");
+        if (!lut.empty()) jpge::detail::check(jpge_set_channel_lut(jpge::default_context(), lut.data()), "lut");
         img.writeJPEG(jpg, quality);
     } catch (const std::exception& e) {
         std::cerr << "jpgenc: " << e.what() << std::endl;

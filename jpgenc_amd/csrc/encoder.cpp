@@ -311,6 +311,32 @@ int Encoder::orientation() {
     return orient_;
 }
 
+int Encoder::set_channel_lut(const uint8_t* lut) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    if (!lut) {
+        lut_on_ = false;
+        return kOk;
+    }
+    // (the call holds the context: no frame is in flight, so the one device copy can be rewritten;
+    // on a stream of the context's own, and awaited: every lane's next launch sees the new bytes,
+    // and the caller's buffer and lut_ are free to change)
+    JPGE_HIP(hipSetDevice(device_));
+    if (!d_lut_) JPGE_HIP(hipMalloc((void**)&d_lut_, kLutBytes));
+    lut_on_ = false;  // (a failed upload leaves the tables off, not half written and on)
+    std::memcpy(lut_, lut, kLutBytes);
+    hipStream_t stream = lanes_[0]->stream;
+    JPGE_HIP(hipMemcpyAsync(d_lut_, lut_, kLutBytes, hipMemcpyHostToDevice, stream));
+    JPGE_HIP(hipStreamSynchronize(stream));
+    lut_on_ = true;
+    return kOk;
+}
+
+void Encoder::channel_lut(int* on, uint8_t* lut) {
+    std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
+    if (on) *on = lut_on_ ? 1 : 0;
+    if (lut) std::memcpy(lut, lut_, kLutBytes);
+}
+
 int Encoder::set_yuv_transform(int preset, const YuvXf* custom) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     YuvXf t;
@@ -561,6 +587,7 @@ Encoder::~Encoder() {
         if (ln->stream) hipStreamDestroy(ln->stream);
     }
     hipFree(d_dbg_);
+    hipFree(d_lut_);
 }
 
 // Diagnostic: raw per-workgroup phase stamps of the last frame, as
@@ -634,6 +661,8 @@ FdctArgs Encoder::fdct_args(Slot& s, int maxval, Slot* imp) {
         a.xf[0] = yuv_xf_.y_off;
         for (int i = 0; i < 7; ++i) a.xf[1 + i] = yuv_xf_.m[i];
     }
+    // the channel tables (prep1 has refused the frames that have no such kernel)
+    if (lut_on_ && lut_fmt(s.in_fmt)) fdct_set_lut(a, d_lut_);
     a.g = s.g;
     a.maxval = maxval;
     a.solo = lanes_.size() == 1;  // (several lanes: K1 runs beside other frames' kernels)
@@ -745,6 +774,8 @@ int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint
     // a Bayer mosaic: bytes as they are, a 2x2 cell at least (a reflected neighbour exists), coded at
     // full size and as it lies (ds_fmt and orient_fmt above refuse the other settings; one plane)
     if (fmt_bayer(f.fmt) && (f.maxval != 255 || f.width < 2 || f.height < 2)) return kErrArg;
+    // channel tables: the layouts that stage R, G, B bytes, as they are, at full size and as they lie
+    if (lut_on_ && (!lut_fmt(f.fmt) || f.maxval != 255 || ds > 1 || orient)) return kErrArg;
     // 10-bit layouts: 16-bit words, so an even base and even pitches
     if (fmt_yuv10(f.fmt) && (((uintptr_t)f.rgb | f.stride | f.plane_stride) & 1)) return kErrArg;
     // (v210: 32-bit words, so a base and a pitch that are multiples of 4)

@@ -169,6 +169,15 @@ class Encoder {
     int set_orientation(int o);
     int orientation();
 
+    // Per-channel lookup tables of the following pixel encodes and stage entries (jpge.h
+    // jpge_set_channel_lut; kernels.hpp kLutBytes): lut = 768 bytes T_R, T_G, T_B, copied, or nullptr
+    // for none (the default).  With tables on K1 maps every pixel it stages, and the frame codes as
+    // the mapped RGB8 frame.  RGB8, BGR8, RGBA8, BGRA8 and the Bayer layouts, maxval 255, no
+    // downscale factor above 1 and no orientation; the stripe phases refuse them.  encode_planes
+    // ignores the setting.  The device copy is uploaded here, on lane 0's stream, and awaited.
+    int set_channel_lut(const uint8_t* lut);
+    void channel_lut(int* on, uint8_t* lut);
+
     int lanes() const { return (int)lanes_.size(); }
 
   private:
@@ -246,6 +255,11 @@ class Encoder {
     int fmt_ = kFmtRgb8;        // input layout (jpge_set_input_format)
     int ds_ = 1;                // box downscale factor (jpge_set_downscale)
     int orient_ = 0;            // orientation (jpge_set_orientation)
+    // channel tables (jpge_set_channel_lut): on or off, the bytes, and their device copy
+    // (allocated at the first setting, freed with the context)
+    bool lut_on_ = false;
+    uint8_t lut_[kLutBytes] = {};
+    uint8_t* d_lut_ = nullptr;
     // Huffman mode (jpge_set_huffman) and, in a fixed mode, the four tables: as given, as
     // codes, and as the [4][256] (len << 16) | code words the code kernel reads (built once,
     // at set_huffman); the generation numbers a setting (a slot remembers whose tables it holds)

@@ -18,6 +18,7 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     if (huff_mode_) return kErrArg;    // and share per-image tables (the histogram all-reduce)
     if (ds_ > 1) return kErrArg;       // and are coded at full size (jpge_set_downscale)
     if (orient_) return kErrArg;       // and as they lie (jpge_set_orientation)
+    if (lut_on_) return kErrArg;       // and with their own values (jpge_set_channel_lut)
     if (fmt_planes(fmt_) != 1 || fmt_gray(fmt_) || fmt_yuv(fmt_)) return kErrArg;  // and interleaved colour (the stripe pointer is one row of pixels)
     if (fmt_bayer(fmt_)) return kErrArg;  // (a mosaic's stripe would need its neighbours' rows)
     if (d.maxval < 1 || d.maxval > 255) return kErrRange;

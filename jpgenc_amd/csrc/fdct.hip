@@ -100,10 +100,20 @@ struct K1WaveLds {
 };
 constexpr int kQRow = 9;  // padded q-table rows: lanes reading rows j=0..7 hit distinct banks
 
+// (JPGE_K1_LUT: the builds that map every staged word through the context's channel tables, see
+// "channel tables" below)
+#ifndef JPGE_K1_LUT
+#define JPGE_K1_LUT 0
+#endif
+constexpr int kLutWords = kLutBytes / 4;
+
 template <int kWaves>
 struct K1Lds {
     K1WaveLds w[kWaves];
     uint32_t next;  // next tile of the workgroup's run to hand out
+#if JPGE_K1_LUT
+    uint32_t lut[kLutWords];  // the frame's channel tables: bytes T_R[0..255], T_G[0..255], T_B[0..255]
+#endif
     double q[2][8 * kQRow];     // luma, chroma
     double invq[2][8 * kQRow];  // s_u / q (correctly rounded), u = column
 };
@@ -239,6 +249,28 @@ constexpr int kOrient = JPGE_K1_ORIENT;
 static_assert(kOrient == 0 || (kOrient >= 1 && kOrient <= 4 && kDs == 1 && kShape <= kShapeX4), "JPGE_K1_ORIENT");
 constexpr bool kOrMirror = kOrient == 2 || kOrient == 4;  // the source's columns run backwards
 constexpr bool kOrTrans = kOrient >= 3;                   // O's rows are the source's columns (fdct_kernel only)
+// ---- channel tables (JPGE_K1_LUT 1; kernels.hpp fdct_lut) ----
+// The builds of the RGB8, BGR8, 4-byte and Bayer shapes for a context with per-channel lookup
+// tables (jpge_set_channel_lut): every staged word R | G<<8 | B<<16 becomes
+// T_R[R] | T_G[G]<<8 | T_B[B]<<16 before it is written to the staged tile, on the fast path and on
+// the byte paths alike (the clamped path fills the same 16 registers; the Bayer shape's rolled byte
+// loop, which writes its words itself, maps each as it writes it).  Everything after the staging
+// reads the mapped frame.  kExact instances, 4-wave workgroups and frame sets only, as the Bayer build.
+// The tables are 768 bytes of LDS, one copy per workgroup, loaded in the prologue from the frame's
+// own pointer.  A channel's 256 bytes are 64 consecutive words, two to each of the 32 banks a 32-bit
+// read sees: lanes that read the same word are served together, so a read of random samples is a
+// 2-way conflict at the worst, whatever the pixels are.  (256 packed words T_R | T_G<<8 | T_B<<16,
+// one b32 read per channel and a byte select, would put eight words in each bank, up to 8-way, and
+// need a scaled address per channel.)  A pixel costs three byte reads at the immediate offsets 0,
+// 256, 512, three field extractions and two v_lshl_or_b32.
+constexpr bool kLut = JPGE_K1_LUT != 0;
+static_assert(!kLut || (kDs == 1 && kOrient == 0 && (kShape == kShapeRgb8 || kShape == kShapeBgr8 || kShape == kShapeX4 || kShape == kShapeBayer8)),
+              "JPGE_K1_LUT");
+// the mapped word of a staged word p (byte 3 of p is zero); t: the workgroup's tables in LDS
+__device__ __forceinline__ uint32_t lut_map(const uint8_t* t, uint32_t p) {
+    const uint32_t r = t[p & 0xFF], g = t[256 + ((p >> 8) & 0xFF)], b = t[512 + (p >> 16)];
+    return r | (g << 8) | (b << 16);
+}
 
 // perm selector of a 3-byte pixel starting at byte o8 of a word pair
 __device__ __forceinline__ constexpr uint32_t sel3(uint32_t o8) {
@@ -704,8 +736,9 @@ __device__ __forceinline__ void unpack_bayer(const uint4& va, const uint4& vm, c
 // rolled.  A coordinate is clamped in the demosaiced frame first (row min(y, gh - 1), column
 // min(xs + i, gw - 1)), and that pixel's neighbours are the reflected ones.  The 3x3 window slides:
 // three byte loads a pixel (a column), by plain pointers, any base and pitch.
+// (lut: the workgroup's channel tables, read by the kLut builds only)
 __device__ __forceinline__ void edge_bayer(const uint8_t* base, uint64_t stride, uint32_t gw, uint32_t gh, uint32_t phase,
-                                           uint32_t y, uint32_t xs, uint32_t* dst) {
+                                           uint32_t y, uint32_t xs, uint32_t* dst, const uint8_t* lut) {
     const uint32_t sy = min(y, gh - 1);
     const uint8_t* ra = base + (uint64_t)bayer_before(sy) * stride;
     const uint8_t* rm = base + (uint64_t)sy * stride;
@@ -722,7 +755,8 @@ __device__ __forceinline__ void edge_bayer(const uint8_t* base, uint64_t stride,
             cx = x;
         }
         r = column(bayer_after(cx, gw));
-        dst[i] = bayer_rgb(phase, sy, cx, l, m, r);
+        if constexpr (kLut) dst[i] = lut_map(lut, bayer_rgb(phase, sy, cx, l, m, r));  // (the channel tables: this path writes its words itself)
+        else dst[i] = bayer_rgb(phase, sy, cx, l, m, r);
     }
 }
 
@@ -945,6 +979,18 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     __shared__ K1Lds<kWaves> lds;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;  // wv: 0..15
     K1WaveLds& W = lds.w[wv];
+    // (the channel tables' builds: the workgroup's copy, and this thread's word of the frame's tables,
+    // loaded ahead of the first tile's pixel loads below: the vector memory counter retires in order,
+    // so the wait for this word before its LDS write leaves the pixel loads in flight)
+    const uint8_t* lut_ = nullptr;
+    uint32_t lut_w_ = 0;
+    if constexpr (kLut) {
+        static_assert(kWaves * 64 >= kLutWords, "a thread loads one word of the tables");
+        lut_ = reinterpret_cast<const uint8_t*>(lds.lut);
+        // (through a descriptor of the 768 bytes, as the pixels: a thread past the tables loads nothing)
+        const __amdgpu_buffer_rsrc_t lut_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(fdct_lut_raw(a)), 0, kLutBytes, 0x00020000);
+        lut_w_ = __builtin_amdgcn_raw_buffer_load_b32(lut_rs, (uint32_t)tid * 4u, 0, 0);
+    }
     JPGE_STAMP(1);
     const uint32_t mw = a.g.mw;
     const uint32_t tiles_per_row = (mw + 3) / 4;
@@ -1101,6 +1147,10 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
     bool cfast;
     if constexpr (kDs > 1) cfast = fast_load_ds(k, nx);
     else cfast = fast_load(k, c0, c1, c2, c3);  // issued before the prologue's own memory traffic
+    // (the channel tables' word, loaded before the pixels: written here, ahead of the loop below, so
+    // that the wait is a count the compiler knows, "all but the pixel loads", not zero)
+    if constexpr (kLut)
+        if (tid < kLutWords) lds.lut[tid] = lut_w_;
 
     for (uint32_t i = bid * kK1Threads + tid; i < a.zero_words; i += nbk * kK1Threads) a.zero[i] = 0;
     if (bid == 0)  // carried: another frame's tables + headers, host -> device
@@ -1302,6 +1352,10 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
             else
                 for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
+        if constexpr (kLut) {  // the channel tables: fast path and clamped path alike
+#pragma unroll
+            for (int i = 0; i < 16; ++i) px[i] = lut_map(lut_, px[i]);
+        }
         if constexpr (kOrTrans) {
             // down column `lane` of the staged tile: the lanes' addresses are consecutive words
 #pragma unroll
@@ -1312,7 +1366,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_kernel(FrameSet<
             for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
             // (Bayer: a lane on the clamped path writes its words over the ones just staged, in a rolled loop)
             if constexpr (kBayer)
-                if (!cfast) edge_bayer(rgb_, stride_, gw_, gh_, phase_, y, xs, dst);
+                if (!cfast) edge_bayer(rgb_, stride_, gw_, gh_, phase_, y, xs, dst, lut_);
         }
         wave_order();
         // prefetch the next tile of this wave (into the registers just staged) while
@@ -1458,6 +1512,18 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
     __shared__ K1Lds<kWaves> lds;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     K1WaveLds& W = lds.w[wv];
+    // (the channel tables' builds: the workgroup's copy, and this thread's word of the frame's tables,
+    // loaded ahead of the first tile's pixel loads below: the vector memory counter retires in order,
+    // so the wait for this word before its LDS write leaves the pixel loads in flight)
+    const uint8_t* lut_ = nullptr;
+    uint32_t lut_w_ = 0;
+    if constexpr (kLut) {
+        static_assert(kWaves * 64 >= kLutWords, "a thread loads one word of the tables");
+        lut_ = reinterpret_cast<const uint8_t*>(lds.lut);
+        // (through a descriptor of the 768 bytes, as the pixels: a thread past the tables loads nothing)
+        const __amdgpu_buffer_rsrc_t lut_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(fdct_lut_raw(a)), 0, kLutBytes, 0x00020000);
+        lut_w_ = __builtin_amdgcn_raw_buffer_load_b32(lut_rs, (uint32_t)tid * 4u, 0, 0);
+    }
     JPGE_STAMP(1);
     const uint32_t mw = a.g.mw;
     const uint32_t tiles_per_row = (mw + kMcus - 1) / kMcus;
@@ -1563,6 +1629,10 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
     bool cfast;
     if constexpr (kDs > 1) cfast = fast_load_ds(k, nx);
     else cfast = fast_load(k, c0, c1, c2, c3);
+    // (the channel tables' word, loaded before the pixels: written here, ahead of the loop below, so
+    // that the wait is a count the compiler knows, "all but the pixel loads", not zero)
+    if constexpr (kLut)
+        if (tid < kLutWords) lds.lut[tid] = lut_w_;
 
     for (uint32_t i = bid * kK1Threads + tid; i < a.zero_words; i += nbk * kK1Threads) a.zero[i] = 0;
     if (bid == 0)
@@ -1650,11 +1720,15 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
             else
                 for (int i = 0; i < 16; ++i) px[i] = edge_pixel(rgb_, stride_, ps_, sel4_, sy, min(xs + i, gw_ - 1));
         }
+        if constexpr (kLut) {  // the channel tables: fast path and clamped path alike
+#pragma unroll
+            for (int i = 0; i < 16; ++i) px[i] = lut_map(lut_, px[i]);
+        }
         uint32_t* dst = &W.rgbx[r8 * kRgbPitch444 + c8 * 16];
 #pragma unroll
         for (int i = 0; i < 16; i += 2) *reinterpret_cast<uint2*>(dst + i) = make_uint2(px[i], px[i + 1]);
         if constexpr (kBayer)  // (as in fdct_kernel)
-            if (!cfast) edge_bayer(rgb_, stride_, gw_, gh_, phase_, y, xs, dst);
+            if (!cfast) edge_bayer(rgb_, stride_, gw_, gh_, phase_, y, xs, dst, lut_);
         wave_order();
         if constexpr (kDs > 1) {
             cfast = fast_load_ds(kn, nx);
@@ -1743,7 +1817,7 @@ __global__ __launch_bounds__(kWaves * 64) JPGE_K1_OCC void fdct_row8_kernel(Fram
 constexpr uint32_t kK1WholeCuTiles = 65536;
 uint32_t k1_tiles(const Geometry& g);
 bool k1_whole_cu(const Geometry& g, bool solo, uint32_t ds = 1, uint32_t orient = 0);
-#if JPGE_K1_SHAPE == 0 && JPGE_K1_DS == 1 && JPGE_K1_ORIENT == 0
+#if JPGE_K1_SHAPE == 0 && JPGE_K1_DS == 1 && JPGE_K1_ORIENT == 0 && JPGE_K1_LUT == 0
 uint32_t k1_tiles(const Geometry& g) {
     const uint32_t per = g.row8() ? 16 / g.yh : 4;  // MCUs per tile
     return ((g.mw + per - 1) / per) * g.mh;
@@ -1766,8 +1840,8 @@ static hipError_t launch_row8(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, h
         if (ex) return hipErrorInvalidValue;
         if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_row8_kernel<false, kK1WavesSolo, kYh, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         return launch_timed(t, fdct_row8_kernel<false, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
-    } else if constexpr (kBayer) {
-        // (the Bayer build has the exact colour path's 4-wave workgroup only: maxval is 255)
+    } else if constexpr (kBayer || kLut) {
+        // (the Bayer build and the channel tables' builds have the exact colour path's 4-wave workgroup only: maxval is 255)
         return !ex ? hipErrorInvalidValue : launch_timed(t, fdct_row8_kernel<true, kK1WavesShared, kYh, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     } else {
         // (the downscaling and the oriented builds have the 4-wave workgroup only: k1_whole_cu is false for them)
@@ -1792,8 +1866,8 @@ static hipError_t launch_420(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hi
         if (ex) return hipErrorInvalidValue;
         if (k1_whole_cu(a.g, a.solo)) return launch_timed(t, fdct_kernel<false, kK1WavesSolo, kFilt, kN>, dim3(grid), dim3(kK1WavesSolo * 64), s, fs);
         return launch_timed(t, fdct_kernel<false, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
-    } else if constexpr (kBayer) {
-        // (the Bayer build has the exact colour path's 4-wave workgroup only: maxval is 255)
+    } else if constexpr (kBayer || kLut) {
+        // (the Bayer build and the channel tables' builds have the exact colour path's 4-wave workgroup only: maxval is 255)
         return !ex ? hipErrorInvalidValue : launch_timed(t, fdct_kernel<true, kK1WavesShared, kFilt, kN>, dim3(grid), dim3(kK1WavesShared * 64), s, fs);
     } else {
         // (the downscaling and the oriented builds have the 4-wave workgroup only: k1_whole_cu is false for them)
@@ -1844,10 +1918,10 @@ static hipError_t launch_k1(const FrameSet<FdctArgs, kN>& fs, uint32_t grid, hip
     }
 }
 
-#if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1 || JPGE_K1_ORIENT != 0
+#if JPGE_K1_SHAPE != 0 || JPGE_K1_DS != 1 || JPGE_K1_ORIENT != 0 || JPGE_K1_LUT != 0
 // this load shape's entry point (JPGE_K1_ENTRY: launch_fdct_bgr8 / _x4 / _planar / _nv12 / _i420 / _yuv444 / _gray /
 // _packed422 / _nv16 / _i422 / _p010 / _i010 / _y210 / _p210 / _i210 / _v210 / _bayer8; the downscaling builds: launch_fdct_rgb8_d2 / _d4, _bgr8_d2, ...;
-// the oriented builds: launch_fdct_rgb8_o1 .. _o4, _bgr8_o1, ...)
+// the oriented builds: launch_fdct_rgb8_o1 .. _o4, _bgr8_o1, ...; the channel tables' builds: launch_fdct_rgb8_lut, _bgr8_lut, _x4_lut, _bayer8_lut)
 hipError_t JPGE_K1_ENTRY(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t) {
     return launch_k1<kMaxSet>(fs, grid, s, t);
 }
@@ -1902,6 +1976,11 @@ JPGE_K1_ORIENT_ENTRIES(rgb8)
 JPGE_K1_ORIENT_ENTRIES(bgr8)
 JPGE_K1_ORIENT_ENTRIES(x4)
 #undef JPGE_K1_ORIENT_ENTRIES
+// the channel tables' builds (kernels.hpp fdct_lut) of the shapes that have them
+hipError_t launch_fdct_rgb8_lut(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_bgr8_lut(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_x4_lut(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
+hipError_t launch_fdct_bayer8_lut(const FrameSet<FdctArgs, kMaxSet>& fs, uint32_t grid, hipStream_t s, const KTimer* t);
 
 uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs, uint32_t ds, uint32_t orient) {
     const uint32_t tiles = k1_tiles(g);
@@ -1917,8 +1996,8 @@ uint32_t fdct_grid(const Geometry& g, bool solo, uint32_t override_wgs, uint32_t
 }
 
 // fdct_grid's last argument for a frame: non-zero rules the whole-CU shape out, for an oriented
-// frame and for a Bayer one (both builds have the 4-wave workgroups only)
-static uint32_t k1_small(const FdctArgs& a) { return fmt_bayer(a.fmt) ? 1u : a.orient; }
+// frame, a Bayer one and one with channel tables (their builds have the 4-wave workgroups only)
+static uint32_t k1_small(const FdctArgs& a) { return fmt_bayer(a.fmt) || fdct_lut(a) ? 1u : a.orient; }
 
 // A set of frames of one geometry, colour path and workgroup shape (one launch).
 template <int kN>
@@ -1937,6 +2016,10 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
         // (a Bayer frame: a 2x2 cell at least, so that a reflected neighbour exists; one plane; the
         // exact colour path.  The members of a set may differ in CFA phase: each reads its own.)
         if (fmt_bayer(m.fmt) && (m.g.width < 2 || m.g.height < 2 || m.maxval != 255 || m.plane_stride)) return hipErrorInvalidValue;
+        // (channel tables: the exact colour path, at full size and as the frame lies; a set is all
+        // with tables or all without: the setting is a context's, and a group's members share it)
+        if (fdct_lut(m) && (m.maxval != 255 || m.ds > 1 || m.orient)) return hipErrorInvalidValue;
+        if ((fdct_lut(m) != nullptr) != (fdct_lut(a) != nullptr)) return hipErrorInvalidValue;
         static_assert(kK1OffsetBound == kOob, "the host's bound is the kernel's out-of-range offset");
         // a downscaled frame: g is the frame of ceil(src / ds) pixels; the offsets span the source
         Geometry src = m.g;
@@ -1972,7 +2055,8 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
             return hipErrorInvalidValue;
     }
     const uint32_t grid = fs.wg0[fs.n];
-    if (a.ds <= 1 && !a.orient && fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
+    const bool lut = fdct_lut(a) != nullptr;
+    if (a.ds <= 1 && !a.orient && !lut && fmt_shape(a.fmt) == kShapeRgb8) return launch_k1(fs, grid, s, t);
     if constexpr (kN == 1) {
         if (fmt_shape(a.fmt) == kShapeP010) return launch_fdct_p010_one(fs, grid, s, t);
         if (fmt_shape(a.fmt) == kShapeI010) return launch_fdct_i010_one(fs, grid, s, t);
@@ -2002,6 +2086,15 @@ static hipError_t launch_fdct_fs(const FrameSet<FdctArgs, kN>& fs, hipStream_t s
             case kShapeBgr8: return d2 ? launch_fdct_bgr8_d2(w, grid, s, t) : launch_fdct_bgr8_d4(w, grid, s, t);
             case kShapeX4: return d2 ? launch_fdct_x4_d2(w, grid, s, t) : launch_fdct_x4_d4(w, grid, s, t);
             case kShapeNv12: return d2 ? launch_fdct_nv12_d2(w, grid, s, t) : launch_fdct_nv12_d4(w, grid, s, t);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    if (lut) {
+        switch (fmt_shape(a.fmt)) {
+            case kShapeRgb8: return launch_fdct_rgb8_lut(w, grid, s, t);
+            case kShapeBgr8: return launch_fdct_bgr8_lut(w, grid, s, t);
+            case kShapeX4: return launch_fdct_x4_lut(w, grid, s, t);
+            case kShapeBayer8: return launch_fdct_bayer8_lut(w, grid, s, t);
             default: return hipErrorInvalidValue;
         }
     }

@@ -298,6 +298,10 @@ int jpge_group_encode_striped(jpge_group* g, const uint8_t* rgb, uint32_t width,
         int orient = JPGE_ORIENT_NONE;
         if (const int st = jpge_get_orientation(c, &orient)) return st;
         if (orient != JPGE_ORIENT_NONE) return (int)JPGE_E_ARG;
+        // and with its own values (the stripe phases refuse channel tables)
+        int lut_on = 0;
+        if (const int st = jpge_get_channel_lut(c, &lut_on, nullptr)) return st;
+        if (lut_on) return (int)JPGE_E_ARG;
     }
     const size_t row = (size_t)width * 3, pitch = stride ? stride : row;
     if (pitch < row) return (int)JPGE_E_ARG;

@@ -245,6 +245,23 @@ static_assert(offsetof(FdctArgs, ds) == 56 && offsetof(FdctArgs, orient) == 60, 
 // (The block has no padding left.  A Bayer frame's CFA phase needs no field: it is bayer_phase(fmt),
 // which each member of a frame set reads from its own block, as the 4-byte shape reads its channel order.)
 
+// Per-channel lookup tables (jpge.h jpge_set_channel_lut): kLutBytes bytes, T[256 c + v] the value of
+// channel c (0 R, 1 G, 2 B) for the sample v.  A frame codes as the RGB8 frame M with
+// M[y][x][c] = T[256 c + D[y][x][c]], D the frame's RGB8 pixels (a Bayer frame: its demosaic), mapped
+// in K1's tile staging (fdct.hip JPGE_K1_LUT).  The interleaved RGB layouts and the Bayer ones, at
+// full size and as they lie.  The RGB and Bayer shapes never read xf, so the device pointer of the
+// context's table lives in that field's first 8 bytes: all zero bits (the default, xf[0] = 0.0) is
+// "no table", and the host writes it only when a table is on.  Each member of a frame set reads
+// its own.
+constexpr int kLutBytes = 768;
+JPGE_HD inline bool lut_fmt(int fmt) { return (fmt >= kFmtRgb8 && fmt <= kFmtBgra8) || fmt_bayer(fmt); }
+JPGE_HD inline const uint8_t* fdct_lut_raw(const FdctArgs& a) {
+    return reinterpret_cast<const uint8_t*>(__builtin_bit_cast(uint64_t, a.xf[0]));
+}
+// (the other shapes' xf is their sample transform)
+JPGE_HD inline const uint8_t* fdct_lut(const FdctArgs& a) { return lut_fmt(a.fmt) ? fdct_lut_raw(a) : nullptr; }
+inline void fdct_set_lut(FdctArgs& a, const uint8_t* d_lut) { a.xf[0] = __builtin_bit_cast(double, (uint64_t)reinterpret_cast<uintptr_t>(d_lut)); }
+
 // Box downscale by 2 or 4 inside K1 (jpge.h jpge_set_downscale): the interleaved RGB layouts in
 // every subsampling mode, and NV12 (whose Cb,Cr plane is averaged in its own domain).
 JPGE_HD inline bool ds_valid(int ds) { return ds == 1 || ds == 2 || ds == 4; }

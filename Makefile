@@ -15,7 +15,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -I$(SR
 CXXFLAGS := -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Wno-unused-parameter -Wno-unused-result \
             -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -I$(SRC) -Iinclude $(HIPEXTRA)
 
-HOST_SRCS := encoder.cpp encoder_stripes.cpp encoder_planes.cpp capi.cpp host_io.cpp huffman.cpp jpge_image.cpp ingest.cpp host_decode.cpp coding.cpp group.cpp
+HOST_SRCS := encoder.cpp frame_plan.cpp encoder_stripes.cpp encoder_planes.cpp capi.cpp host_io.cpp huffman.cpp jpge_image.cpp ingest.cpp host_decode.cpp coding.cpp group.cpp
 HOST_OBJS := $(addprefix $(BUILD)/,$(HOST_SRCS:.cpp=.o))
 # (fdct_*_d2 / _d4: the shapes' box-downscaling builds, jpge_set_downscale)
 K1_DS_SRCS := fdct_rgb8_d2.hip fdct_rgb8_d4.hip fdct_bgr8_d2.hip fdct_bgr8_d4.hip fdct_x4_d2.hip fdct_x4_d4.hip fdct_nv12_d2.hip fdct_nv12_d4.hip
@@ -33,8 +33,10 @@ QUANT_TEST  := tests/cpp/bin/test_quant_fast
 EXIT_TEST   := tests/cpp/bin/test_exit_close
 HUFFSPEC_TEST := tests/cpp/bin/test_huffspec
 YUVXF_TEST  := tests/cpp/bin/test_yuvxf
+PLAN_TEST   := tests/cpp/bin/test_frame_plan
+PLAN_DEPS   := tests/cpp/test_frame_plan.cpp $(SRC)/frame_plan.cpp $(SRC)/frame_plan.hpp $(SRC)/layouts.hpp $(SRC)/kernels.hpp $(SRC)/host_io.hpp
 
-all: $(LIBDIR)/libjpge.so $(BINDIR)/jpgenc $(FACADE_TEST) $(HUFF_TEST) $(QUANT_TEST) $(EXIT_TEST) $(HUFFSPEC_TEST) $(YUVXF_TEST) oracle
+all: $(LIBDIR)/libjpge.so $(BINDIR)/jpgenc $(FACADE_TEST) $(HUFF_TEST) $(QUANT_TEST) $(EXIT_TEST) $(HUFFSPEC_TEST) $(YUVXF_TEST) $(PLAN_TEST) oracle
 
 # (fdct_*.hip: fdct.hip built per input load shape)
 K1_SHAPES := fdct_bgr8.o fdct_x4.o fdct_planar.o fdct_nv12.o fdct_i420.o fdct_yuv444.o fdct_gray.o fdct_packed422.o fdct_nv16.o fdct_i422.o fdct_p010.o fdct_i010.o fdct_y210.o fdct_p210.o fdct_i210.o fdct_v210.o fdct_bayer8.o $(K1_DS_SRCS:.hip=.o) $(K1_OR_SRCS:.hip=.o) $(K1_LUT_SRCS:.hip=.o)
@@ -113,6 +115,12 @@ $(YUVXF_TEST): tests/cpp/test_yuvxf.cpp $(SRC)/host_io.cpp $(SRC)/host_io.hpp $(
 	@mkdir -p tests/cpp/bin
 	$(CXX) $(CXXFLAGS) -o $@ $< $(SRC)/host_io.cpp
 
+# the layout table, the frame plan's refusals and its upload layout, host only: no HIP library
+# is linked (tests/test_frame_plan_cpu.py runs it)
+$(PLAN_TEST): $(PLAN_DEPS)
+	@mkdir -p tests/cpp/bin
+	$(CXX) $(CXXFLAGS) -o $@ $< $(SRC)/frame_plan.cpp
+
 # Host code under AddressSanitizer + UndefinedBehaviorSanitizer (run by
 # tests/test_asan.py in the CPU suite): every host .cpp of the library rebuilt
 # sanitized and linked with the (unsanitized) HIP device objects, plus the host
@@ -122,7 +130,7 @@ ASAN_DIR   := build/asan
 ASAN_BIN   := tests/cpp/bin/asan
 ASAN_OBJS  := $(addprefix $(ASAN_DIR)/,$(HOST_SRCS:.cpp=.o))
 ASAN_TESTS := $(ASAN_BIN)/test_host_asan $(ASAN_BIN)/test_facade $(ASAN_BIN)/test_huffman_fast $(ASAN_BIN)/test_quant_fast \
-              $(ASAN_BIN)/test_huffspec $(ASAN_BIN)/test_yuvxf
+              $(ASAN_BIN)/test_huffspec $(ASAN_BIN)/test_yuvxf $(ASAN_BIN)/test_frame_plan
 
 $(ASAN_DIR)/%.o: $(SRC)/%.cpp $(HEADERS)
 	@mkdir -p $(ASAN_DIR)
@@ -151,6 +159,10 @@ $(ASAN_BIN)/test_huffspec: tests/cpp/test_huffspec.cpp $(SRC)/host_io.cpp $(SRC)
 $(ASAN_BIN)/test_yuvxf: tests/cpp/test_yuvxf.cpp $(SRC)/host_io.cpp $(SRC)/host_io.hpp $(SRC)/huffman.hpp $(SRC)/host_par.hpp
 	@mkdir -p $(ASAN_BIN)
 	$(CXX) $(CXXFLAGS) $(ASAN_FLAGS) -o $@ $< $(SRC)/host_io.cpp
+
+$(ASAN_BIN)/test_frame_plan: $(PLAN_DEPS)
+	@mkdir -p $(ASAN_BIN)
+	$(CXX) $(CXXFLAGS) $(ASAN_FLAGS) -o $@ $< $(SRC)/frame_plan.cpp
 
 asan: $(ASAN_TESTS)
 

@@ -468,7 +468,7 @@ int jpge_get_channel_lut(jpge_ctx* ctx, int* on, uint8_t* lut) {
 
 int jpge_lut_frame(int format, const uint8_t* src, uint32_t w, uint32_t h, size_t stride, const uint8_t* lut, uint8_t* dst,
                    size_t dst_stride) {
-    if (!jpge::orient_fmt(format) || !src || !dst || !lut || !w || !h) return JPGE_E_ARG;  // (the four interleaved layouts)
+    if (!jpge::fmt_rgb4(format) || !src || !dst || !lut || !w || !h) return JPGE_E_ARG;
     const size_t bpp = jpge::fmt_bpp(format), row = bpp * w;
     if (!stride) stride = row;
     if (!dst_stride) dst_stride = row;

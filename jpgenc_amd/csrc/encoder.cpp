@@ -418,18 +418,7 @@ int Encoder::fixed_tables(Slot& s, bool& fresh) {
     return kOk;
 }
 
-size_t Encoder::max_jpeg_bytes(uint32_t w, uint32_t h) {
-    // header <= 20 + 2*69 + 19 + 4*(4+17+256) + 14 ; entropy <= 1665 bits/block,
-    // doubled for worst-case 0xFF stuffing; + EOI.
-    // Restart intervals add per MCU at most an RST marker, a fill byte and its stuffing.
-    // (The largest bound over the MCU shapes: one capacity serves every mode.)
-    size_t cap = 0;
-    for (int mode : {420, 444, 422, 411}) {
-        const Geometry g = geometry(w, h, mode);
-        cap = std::max(cap, 2048 + (size_t)g.nblocks() * 2 * 209 + 16 + (size_t)g.nmcu() * 4);
-    }
-    return cap;
-}
+size_t Encoder::max_jpeg_bytes(uint32_t w, uint32_t h) { return jpge::max_jpeg_bytes(w, h); }
 
 int Encoder::open(int device, std::unique_ptr<Encoder>& out, int lanes) {
     int n = 0;
@@ -646,23 +635,23 @@ SegLayout Encoder::slot_layout(const Slot& s) const {
 FdctArgs Encoder::fdct_args(Slot& s, int maxval, Slot* imp) {
     const CtlLayout L(slot_layout(s).grid());
     FdctArgs a;
-    a.rgb = s.in_dev;
-    a.stride = s.in_stride;
-    a.fmt = s.in_fmt;
-    a.plane_stride = s.in_plane_stride;
-    a.ds = (uint32_t)s.ds;
-    a.orient = (uint32_t)s.orient;
-    a.src_w = s.src_w;
-    a.src_h = s.src_h;
+    a.rgb = s.in.ptr;
+    a.stride = s.in.stride;
+    a.fmt = s.in.fmt;
+    a.plane_stride = s.in.plane_stride;
+    a.ds = (uint32_t)s.in.ds;
+    a.orient = (uint32_t)s.in.orient;
+    a.src_w = s.in.src_w;
+    a.src_h = s.in.src_h;
     // the sample transform of Y, Cb, Cr and gray frames (FULL_601: the kExact instances)
     // (10-bit samples always: FULL_601 runs it with the identity, for its clamps)
-    a.xf_on = ((fmt_yuv(s.in_fmt) || fmt_gray(s.in_fmt)) && yuv_preset_ != kYuvFull601) || fmt_yuv10(s.in_fmt) ? 1u : 0u;
+    a.xf_on = ((fmt_yuv(s.in.fmt) || fmt_gray(s.in.fmt)) && yuv_preset_ != kYuvFull601) || fmt_yuv10(s.in.fmt) ? 1u : 0u;
     if (a.xf_on) {
         a.xf[0] = yuv_xf_.y_off;
         for (int i = 0; i < 7; ++i) a.xf[1 + i] = yuv_xf_.m[i];
     }
-    // the channel tables (prep1 has refused the frames that have no such kernel)
-    if (lut_on_ && lut_fmt(s.in_fmt)) fdct_set_lut(a, d_lut_);
+    // the channel tables (plan_frame has refused the frames that have no such kernel)
+    if (lut_on_ && lut_fmt(s.in.fmt)) fdct_set_lut(a, d_lut_);
     a.g = s.g;
     a.maxval = maxval;
     a.solo = lanes_.size() == 1;  // (several lanes: K1 runs beside other frames' kernels)
@@ -745,93 +734,24 @@ EntropyArgs Encoder::entropy_args(Slot& s) {
     return e;
 }
 
-// Phase 1: upload (if host input), statistics kernels, histogram read-back.
+// Phase 1's host half: the plan (every refusal but the quantisers', before a slot grows or
+// anything is queued), the upload of a host frame, the slot's state and the kernels' arguments.
 int Encoder::prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags,
                    Slot* imp, FdctArgs& a, StatsArgs& st) {
-    if (!f.rgb || f.width == 0 || f.height == 0 || f.width > 65535 || f.height > 65535) return kErrArg;
-    if (f.maxval < 1 || f.maxval > 255) return kErrRange;
-    // (one component: no chroma, so the subsampling mode does not enter, and qc is not read)
-    const bool gray = fmt_gray(f.fmt);
-    // a downscaled frame: f is the source (its limits, pitches and upload are the source's), and
-    // the geometry of everything K1 writes is that of the frame of ceil(f / ds) pixels
-    const int ds = ds_;
-    if (ds > 1 && !ds_fmt(f.fmt)) return kErrArg;  // (the layouts without a downscaling kernel)
-    // an oriented frame, likewise: f is the source, everything K1 writes is the oriented frame's
-    // (the layouts and modes without an oriented kernel; not together with a downscale)
-    const int orient = orient_;
-    if (orient && (!orient_fmt(f.fmt) || ds > 1)) return kErrArg;
-    const uint32_t out_w = orient ? orient_w(f.width, f.height, orient) : ds_dim(f.width, ds),
-                   out_h = orient ? orient_h(f.width, f.height, orient) : ds_dim(f.height, ds);
-    const Geometry g = gray ? gray_geometry(out_w, out_h) : geometry(out_w, out_h, mode_);
-    if (orient_transposed(orient) && g.row8()) return kErrArg;  // (the transposed kernels are the 16x16-MCU ones)
-    Geometry src = g;  // (the extent K1's offsets span)
-    src.width = f.width;
-    src.height = f.height;
-    if (!fmt_valid(f.fmt) || (f.plane_stride && fmt_planes(f.fmt) == 1)) return kErrArg;
-    // Y, Cb, Cr samples are 8-bit, and half-size chroma planes are the S420_m mode's planes
-    if (fmt_yuv(f.fmt) && (f.maxval != 255 || (fmt_yuv420(f.fmt) && mode_ != 420))) return kErrArg;
-    if (gray && f.maxval != 255) return kErrArg;
-    // a Bayer mosaic: bytes as they are, a 2x2 cell at least (a reflected neighbour exists), coded at
-    // full size and as it lies (ds_fmt and orient_fmt above refuse the other settings; one plane)
-    if (fmt_bayer(f.fmt) && (f.maxval != 255 || f.width < 2 || f.height < 2)) return kErrArg;
-    // channel tables: the layouts that stage R, G, B bytes, as they are, at full size and as they lie
-    if (lut_on_ && (!lut_fmt(f.fmt) || f.maxval != 255 || ds > 1 || orient)) return kErrArg;
-    // 10-bit layouts: 16-bit words, so an even base and even pitches
-    if (fmt_yuv10(f.fmt) && (((uintptr_t)f.rgb | f.stride | f.plane_stride) & 1)) return kErrArg;
-    // (v210: 32-bit words, so a base and a pitch that are multiples of 4)
-    if (f.fmt == kFmtV210 && (((uintptr_t)f.rgb | f.stride) & 3)) return kErrArg;
-    if (gray) qc = qy;
-    const size_t row = (size_t)fmt_row_bytes(f.fmt, f.width);
-    const size_t stride = f.stride ? f.stride : row;
-    if (stride < row) return kErrArg;
-    const size_t planes = fmt_planes(f.fmt);
-    const size_t plane_stride = f.plane_stride ? f.plane_stride : stride * f.height;  // (planar)
-    // the device copy of a host frame: the same layout at pitch dev_pitch, plane stride
-    // dev_pitch * height (I420: a 16-byte aligned chroma pitch, half of it)
-    // (the packed 4:2:2 layouts are one plane of rows, NV16 two equal planes: the generic
-    // copies; I422 has I420's chroma planes with a row per pixel row; Y210, P210 and I210 are
-    // to P010 and I010 what the packed layouts, NV16 and I422 are to NV12 and I420)
-    const bool half = fmt_yuv420(f.fmt) || f.fmt == kFmtI422 || f.fmt == kFmtI210;
-    // (v210: its conventional pitch, rows of 48 pixels in 128 bytes)
-    const size_t dev_pitch = f.fmt == kFmtV210 ? 128 * (((size_t)f.width + 47) / 48)
-                                               : align_up(row, f.fmt == kFmtI420 || f.fmt == kFmtI422 || f.fmt == kFmtI010 || f.fmt == kFmtI210 ? 32 : 16);
-    const size_t dev_plane = dev_pitch * f.height;
-    const size_t crows = f.fmt == kFmtI422 || f.fmt == kFmtI210 ? f.height : chroma_dim(f.height),
-                 crow = f.fmt == kFmtNv12 || f.fmt == kFmtP010 ? row : (size_t)fmt_bpp(f.fmt) * chroma_dim(f.width);  // (4:2:0 layouts, I422, I210)
-    const size_t cpitch = (size_t)fmt_chroma_pitch(f.fmt, stride), dev_cpitch = (size_t)fmt_chroma_pitch(f.fmt, dev_pitch);
-    const size_t dev_bytes = half ? dev_plane + (planes - 1) * dev_cpitch * crows : planes * dev_plane;
-    const bool dev_in = (flags & kFlagDeviceInput) != 0, dev_out = (flags & kFlagDeviceOutput) != 0;
-    // the kernel's 32-bit offsets must span the frame it reads (a device frame in place at its
-    // own pitch, a host frame's copy): refused here, before a slot grows or anything is queued
-    if (!k1_offsets_fit(f.fmt, src, dev_in ? stride : dev_pitch)) return kErrArg;
-    const size_t in_bytes = dev_in ? 0 : dev_bytes;
-    const size_t out_cap = dev_out ? 0 : max_jpeg_bytes(out_w, out_h);
+    FramePlan p;
+    if (const int st0 = plan_frame(f, plan_settings(), flags, p)) return st0;
+    if (p.g.gray()) qc = qy;  // (one component: qc is not read)
     if (!tables_nonzero(qy, qc)) return kErrArg;
-    const int st0 = ensure(s, g, in_bytes, out_cap);
-    if (st0) return st0;
-    if (!dev_in) {
-        // (planar: the planes one after the other, dev_pitch * height bytes each)
-        if (stride == dev_pitch && (planes == 1 || plane_stride == dev_plane))
-            // one linear copy (a 2D copy can fall back to a slower engine path)
-            // (v210: up to the last row's last group; a capture row's padding need not be there)
-            JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, f.fmt == kFmtV210 ? dev_bytes - dev_pitch + row : dev_bytes,
-                                    hipMemcpyHostToDevice, s.stream));
-        else if (half) {
-            // the Y plane, then the chroma plane(s): NV12 one of Cb,Cr pairs, I420 Cb then Cr
-            JPGE_HIP(hipMemcpy2DAsync(s.d_in, dev_pitch, f.rgb, stride, (size_t)fmt_bpp(f.fmt) * f.width, f.height, hipMemcpyHostToDevice,
-                                      s.stream));
-            for (size_t c = 0; c + 1 < planes; ++c)
-                JPGE_HIP(hipMemcpy2DAsync(s.d_in + dev_plane + c * dev_cpitch * crows, dev_cpitch,
-                                          f.rgb + plane_stride + c * cpitch * crows, cpitch, crow, crows,
-                                          hipMemcpyHostToDevice, s.stream));
-        } else
-            for (size_t c = 0; c < planes; ++c)
-                JPGE_HIP(hipMemcpy2DAsync(s.d_in + c * dev_plane, dev_pitch, f.rgb + c * plane_stride, stride, row,
-                                          f.height, hipMemcpyHostToDevice, s.stream));
+    if (const int st0 = ensure(s, p.g, p.in_bytes, p.out_cap)) return st0;
+    if (p.linear) JPGE_HIP(hipMemcpyAsync(s.d_in, f.rgb, p.linear, hipMemcpyHostToDevice, s.stream));
+    for (int c = 0; c < p.ncopy; ++c) {
+        const CopyRect& r = p.copy[c];
+        JPGE_HIP(hipMemcpy2DAsync(s.d_in + r.dst_off, r.dst_pitch, f.rgb + r.src_off, r.src_pitch, r.row_bytes, r.rows,
+                                  hipMemcpyHostToDevice, s.stream));
     }
-    s.begin(g, qy, qc, dev_in ? f.rgb : s.d_in, dev_in ? stride : dev_pitch, f.fmt,
-            planes > 1 ? (dev_in ? plane_stride : dev_plane) : 0, dev_out ? f.out : s.d_out,
-            dev_out ? f.cap : s.cap_out, restart_mcus_, out_w, out_h, ds, ds > 1 || orient ? f.width : 0, ds > 1 || orient ? f.height : 0, orient);
+    if (!p.in.ptr) p.in.ptr = s.d_in;  // (a host frame: K1 reads the copy)
+    const bool dev_out = (flags & kFlagDeviceOutput) != 0;
+    s.begin(p.g, qy, qc, p.in, dev_out ? f.out : s.d_out, dev_out ? f.cap : s.cap_out, restart_mcus_, p.g.width, p.g.height);
     if (flags & kFlagFixedTables) {
         // fixed Huffman tables: the frame's own transform kernel carries its code words and
         // headers to the device, where they are new there
@@ -1133,7 +1053,9 @@ int Encoder::encode(FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], ui
     // kFirstSleepMaxPixels: the helper spins from here to the histograms, which take
     // milliseconds there, for tables that are a small part of such a call.
     TableHelper* helper = nullptr;
-    const uint64_t npx = (uint64_t)ds_dim(f.width, ds_) * ds_dim(f.height, ds_);  // (the coded frame's; an oriented one's is the source's)
+    uint32_t cw, ch;  // (the coded frame's pixels)
+    coded_size(f.width, f.height, plan_settings(), &cw, &ch);
+    const uint64_t npx = (uint64_t)cw * ch;
     if (!st && table_helper_ && lanes_.size() == 1 && npx >= (1u << 20) && npx <= kFirstSleepMaxPixels) {
         if (!helper_) helper_.reset(new TableHelper());
         helper = helper_.get();
@@ -1279,9 +1201,9 @@ int Encoder::batch_set_size(const FrameDesc* fr, int n) const {
     const bool placed_in_code = (ext_place_ > 0 || (ext_place_ < 0 && lanes_.size() > 1)) && place_in_code_;
     // (downscaled frames: one source size and one factor give one output geometry, which is
     // the one the kernels after K1 and the set's size go by)
-    // (oriented frames: the oriented frame's, likewise; prep1 refuses both settings together)
-    const uint32_t w0 = orient_ ? orient_w(f0.width, f0.height, orient_) : ds_dim(f0.width, ds_),
-                   h0 = orient_ ? orient_h(f0.width, f0.height, orient_) : ds_dim(f0.height, ds_);
+    // (oriented frames: the oriented frame's, likewise; plan_frame refuses both settings together)
+    uint32_t w0, h0;
+    coded_size(f0.width, f0.height, plan_settings(), &w0, &h0);
     const Geometry g0 = fmt_gray(f0.fmt) ? gray_geometry(w0, h0) : geometry(w0, h0, mode_);
     if (!placed_in_code || restart_mcus_ || layout(g0).grid() > kPlaceInCodeMaxWgs) return 1;
     if (set_) return set_;

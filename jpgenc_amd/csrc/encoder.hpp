@@ -15,33 +15,13 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "frame_plan.hpp"
 #include "host_io.hpp"
 #include "huffman.hpp"
 #include "kernels.hpp"
 #include "planes.hpp"
 
 namespace jpge {
-
-constexpr uint32_t kFlagDeviceInput = 1u;
-constexpr uint32_t kFlagDeviceOutput = 2u;
-constexpr uint32_t kFlagCoefficients = 1u << 30;  // (internal) the frame's coefficients are read back
-constexpr uint32_t kFlagFixedTables = 1u << 29;   // (internal) the frame is coded with the context's fixed Huffman tables
-
-struct FrameDesc {
-    const uint8_t* rgb = nullptr;
-    uint32_t width = 0, height = 0;
-    size_t stride = 0;  // bytes per input row (0 = width * the layout's bytes per pixel)
-    int maxval = 255;
-    // input layout (kernels.hpp kFmt*); planar: plane c at rgb + c * plane_stride
-    // (0 = stride * height).  The C ABI's pixel entries fill these from the context's
-    // setting; the PPM entries leave the default.
-    int fmt = kFmtRgb8;
-    size_t plane_stride = 0;
-    uint8_t* out = nullptr;
-    size_t cap = 0;
-    size_t len = 0;
-    int status = 0;
-};
 
 struct KernelTimes {  // milliseconds of the last timed frame (each kernel's own events, KTimer)
     float fdct = 0, dc_stats = 0, entropy = 0, total = 0;
@@ -193,7 +173,8 @@ class Encoder {
     // (carries `imp`'s tables to the device; exports its own histograms if asked)
     int phase1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags, Slot* imp,
                bool export_hist);
-    // phase 1's host half: validate, size the slot, record the frame's state, the kernels' arguments
+    // phase 1's host half: the frame's plan (frame_plan.hpp: refusals, geometry, upload layout), the
+    // slot sized, the plan's copies queued, the frame's state recorded, the kernels' arguments
     int prep1(Slot& s, const FrameDesc& f, const uint8_t qy[64], const uint8_t qc[64], uint32_t flags, Slot* imp,
               FdctArgs& a, StatsArgs& st);
     // phase 1 of a frame set (kernels.hpp FrameSet: one transform and one statistics
@@ -255,6 +236,7 @@ class Encoder {
     int fmt_ = kFmtRgb8;        // input layout (jpge_set_input_format)
     int ds_ = 1;                // box downscale factor (jpge_set_downscale)
     int orient_ = 0;            // orientation (jpge_set_orientation)
+    PlanSettings plan_settings() const { return {mode_, ds_, orient_, lut_on_}; }
     // channel tables (jpge_set_channel_lut): on or off, the bytes, and their device copy
     // (allocated at the first setting, freed with the context)
     bool lut_on_ = false;

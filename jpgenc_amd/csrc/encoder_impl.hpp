@@ -17,47 +17,6 @@ namespace jpge {
         if ((expr) != hipSuccess) return kErrHip;        \
     } while (0)
 
-// MCU shape of a subsampling mode (jpge.h JPGE_S*): Y blocks across, blocks per MCU
-// and the 4:2:0 chroma filter; false for an unknown mode.
-inline bool mode_shape(int mode, uint32_t& yh, uint32_t& bpm, uint32_t& cfilt) {
-    cfilt = kFiltS420m;
-    switch (mode) {
-        case 420: yh = 2; bpm = 6; return true;
-        case 4201: yh = 2; bpm = 6; cfilt = kFiltS420lm; return true;
-        case 4200: yh = 2; bpm = 6; cfilt = kFiltS420; return true;
-        case 444: yh = 1; bpm = 3; return true;
-        case 422: yh = 2; bpm = 4; return true;
-        case 411: yh = 4; bpm = 6; return true;
-        default: return false;
-    }
-}
-
-// The frame in whole MCUs (4:2:0: 16x16 px, the reference's padding, Image.cpp:480-531;
-// the other modes pad to their own MCU size: edge replication either way)
-inline Geometry geometry(uint32_t w, uint32_t h, int mode = 420) {
-    Geometry g;
-    g.width = w;
-    g.height = h;
-    mode_shape(mode, g.yh, g.bpm, g.cfilt);
-    g.mw = (w + g.mcu_w() - 1) / g.mcu_w();
-    g.mh = (h + g.mcu_h() - 1) / g.mcu_h();
-    return g;
-}
-
-// One component (kFmtGray8): the frame in single 8x8 blocks, no chroma (kernels.hpp Geometry)
-inline Geometry gray_geometry(uint32_t w, uint32_t h) {
-    Geometry g;
-    g.width = w;
-    g.height = h;
-    g.yh = 1;
-    g.bpm = 1;
-    g.mw = (w + 7) / 8;
-    g.mh = (h + 7) / 8;
-    return g;
-}
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Host-side wait with low wake-up latency (the pipeline waits on short intervals).
 hipError_t wait_event(hipEvent_t e);
 
@@ -152,17 +111,7 @@ struct Encoder::Slot {
                                    // ([0, 4)); [6]: encode()'s gate word (gate())
     uint64_t* d_result_host = nullptr;
     // per-frame state between phases (begin() writes it)
-    const uint8_t* in_dev = nullptr;
-    size_t in_stride = 0;
-    int in_fmt = kFmtRgb8;         // the input's layout (kernels.hpp kFmt*)
-    size_t in_plane_stride = 0;
-    // box downscale (jpge_set_downscale): ds > 1: the input is a src_w x src_h frame at in_stride,
-    // and g, img_w, img_h and everything after K1 are the frame of ceil(src / ds) pixels
-    int ds = 1;
-    uint32_t src_w = 0, src_h = 0;
-    // orientation (jpge_set_orientation): non-zero: the input is the src_w x src_h source, and g,
-    // img_w, img_h and everything after K1 are the oriented frame
-    int orient = 0;
+    FrameInput in;  // what K1 reads (frame_plan.hpp; a null in.ptr: the slot holds no frame)
     uint8_t* out_dev = nullptr;
     size_t out_cap = 0;
     size_t hdr_len = 0;
@@ -207,20 +156,12 @@ struct Encoder::Slot {
     // share lane 0's first slot).  A whole frame: zero DC seeds and key bases, its first
     // MCU the image's, untimed until phase 1 says otherwise.  A stripe then sets its
     // keys and rst.mcu0.  (img_w, img_h: the header's dimensions.)
-    void begin(const Geometry& geo, const uint8_t y[64], const uint8_t c[64], const uint8_t* in, size_t stride, int fmt,
-               size_t plane_stride, uint8_t* out, size_t cap, uint32_t restart, uint32_t w, uint32_t h, int factor = 1,
-               uint32_t source_w = 0, uint32_t source_h = 0, int orientation = 0) {
-        ds = factor;
-        orient = orientation;
-        src_w = source_w;
-        src_h = source_h;
+    void begin(const Geometry& geo, const uint8_t y[64], const uint8_t c[64], const FrameInput& input, uint8_t* out, size_t cap,
+               uint32_t restart, uint32_t w, uint32_t h) {
+        in = input;
         std::memcpy(qy, y, 64);
         std::memcpy(qc, c, 64);
         g = geo;
-        in_dev = in;
-        in_stride = stride;
-        in_fmt = fmt;
-        in_plane_stride = plane_stride;
         out_dev = out;
         out_cap = cap;
         seed = DcSeed();

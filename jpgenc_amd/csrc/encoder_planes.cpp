@@ -224,8 +224,9 @@ int Encoder::encode_planes(const double* const planes[3], uint32_t rows, uint32_
     // applySubsampling(S420_m), Image.cpp:842 (Cr, then Cb: independent planes)
     for (int c = 0; c < 2; ++c) JPGE_HIP(launch_plane_subsample(subsample_args(420, p[1 + c], rows, cols, sub[c]), st));
     // (the input pointer marks the slot in use; K1 is not run)
-    s.begin(g, qy, qc, reinterpret_cast<const uint8_t*>(p[0]), 0, kFmtRgb8, 0, dev_out ? out : s.d_out,
-            dev_out ? cap : s.cap_out, restart_mcus_, real_w, real_h);
+    FrameInput in;
+    in.ptr = reinterpret_cast<const uint8_t*>(p[0]);
+    s.begin(g, qy, qc, in, dev_out ? out : s.d_out, dev_out ? cap : s.cap_out, restart_mcus_, real_w, real_h);
     // applyDCT(Arai) + applyQuantization (Image.cpp:844-871) into the MCU layout; the
     // control block is zeroed here (K1 does it on the RGB8 path)
     const CtlLayout L(layout(g).grid());

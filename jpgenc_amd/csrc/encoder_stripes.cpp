@@ -13,18 +13,12 @@ namespace jpge {
 int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const uint8_t qc[64], int32_t last_dc[3]) {
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
+    if (!stripe_settings_ok(fmt_, plan_settings(), huff_mode_ != 0)) return kErrArg;
     if (!d.rgb || !last_dc || d.width == 0 || d.height == 0 || d.width > 65535 || d.height > 65535) return kErrArg;
-    if (mode_ != 420) return kErrArg;  // stripes are S420_m (the reference's subsampling)
-    if (huff_mode_) return kErrArg;    // and share per-image tables (the histogram all-reduce)
-    if (ds_ > 1) return kErrArg;       // and are coded at full size (jpge_set_downscale)
-    if (orient_) return kErrArg;       // and as they lie (jpge_set_orientation)
-    if (lut_on_) return kErrArg;       // and with their own values (jpge_set_channel_lut)
-    if (fmt_planes(fmt_) != 1 || fmt_gray(fmt_) || fmt_yuv(fmt_)) return kErrArg;  // and interleaved colour (the stripe pointer is one row of pixels)
-    if (fmt_bayer(fmt_)) return kErrArg;  // (a mosaic's stripe would need its neighbours' rows)
     if (d.maxval < 1 || d.maxval > 255) return kErrRange;
     const uint32_t mh_img = (d.height + 15) / 16;
     if (d.mcu_rows == 0 || d.mcu_row0 >= mh_img || d.mcu_rows > mh_img - d.mcu_row0) return kErrArg;
-    const size_t row = (size_t)d.width * fmt_bpp(fmt_), stride = d.stride ? d.stride : row;
+    const size_t row = (size_t)fmt_row_bytes(fmt_, d.width), stride = d.stride ? d.stride : row;
     if (stride < row) return kErrArg;
     if (!tables_nonzero(qy, qc)) return kErrArg;
     const uint32_t hs = std::min(16 * d.mcu_rows, d.height - 16 * d.mcu_row0);
@@ -35,7 +29,11 @@ int Encoder::stripe_transform(const StripeDesc& d, const uint8_t qy[64], const u
     Slot& s = slot0();
     if (const int st = ensure(s, g, 0, 0)) return st;
     // (no output yet: stripe_code sizes the headers without one, stripe_pack takes the caller's)
-    s.begin(g, qy, qc, d.rgb, stride, fmt_, 0, nullptr, 0, restart_mcus_, d.width, d.height);
+    FrameInput in;
+    in.ptr = d.rgb;
+    in.stride = stride;
+    in.fmt = fmt_;
+    s.begin(g, qy, qc, in, nullptr, 0, restart_mcus_, d.width, d.height);
     s.rst.mcu0 = d.mcu_row0 * g.mw;
     s.key_y0 = 2ull * d.mcu_row0 * (2ull * g.mw);  // Y blocks above the stripe (raster)
     s.key_c0 = (uint64_t)d.mcu_row0 * g.mw;         // Cb blocks above it
@@ -55,7 +53,7 @@ int Encoder::stripe_stats(const int32_t seed[3], uint32_t counts[1024], uint64_t
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = slot0();
-    if (!s.in_dev || !seed || !counts || !first || huff_mode_) return kErrArg;
+    if (!s.in.ptr || !seed || !counts || !first || huff_mode_) return kErrArg;
     for (int c = 0; c < 3; ++c) s.seed.v[c] = seed[c];
     const StatsArgs st = stats_args(s);
     JPGE_HIP(launch_stats(st, s.stream));
@@ -78,7 +76,7 @@ int Encoder::stripe_code(const uint32_t counts[1024], const uint64_t first[1024]
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = slot0();
-    if (!s.in_dev || !counts || !first || !sum || huff_mode_) return kErrArg;
+    if (!s.in.ptr || !counts || !first || !sum || huff_mode_) return kErrArg;
     s.out_dev = nullptr;
     s.out_cap = 0;
     if (const int st = build_tables_from(s, counts, first, true)) return st;
@@ -144,7 +142,7 @@ int Encoder::stripe_pack(const StripeSummary* all, int n, int index, uint8_t* ou
     std::lock_guard<std::recursive_mutex> call_lock(call_mu_);
     JPGE_HIP(hipSetDevice(device_));
     Slot& s = slot0();
-    if (!s.in_dev || !out_dev || !s.hdr_len || huff_mode_) return kErrArg;
+    if (!s.in.ptr || !out_dev || !s.hdr_len || huff_mode_) return kErrArg;
     uint64_t p_ext = 0, q_ext = 0;
     uint32_t head = 0;
     size_t off = 0, total = 0;

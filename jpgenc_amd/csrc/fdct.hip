@@ -22,6 +22,7 @@
 
 #include "arai.hpp"
 #include "device_common.hpp"
+#include "layouts.hpp"  // (the host launcher's questions about a layout)
 
 namespace jpge {
 namespace {

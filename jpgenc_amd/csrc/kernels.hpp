@@ -54,7 +54,8 @@ struct Geometry {
 JPGE_HD inline int block_comp(int k, uint32_t bpm) { return bpm == 1 || k < (int)bpm - 2 ? 0 : k - ((int)bpm - 3); }
 
 // Input layouts (jpge.h JPGE_FMT_*, the same values) and K1's load shapes: what a lane
-// loads for its 16-pixel run.  Each shape is one build of fdct.hip (JPGE_K1_SHAPE).
+// loads for its 16-pixel run.  Each shape is one build of fdct.hip (JPGE_K1_SHAPE).  layouts.hpp has
+// each layout's row: its shape, row and plane arithmetic, families and capabilities (host code).
 constexpr int kFmtRgb8 = 0, kFmtBgr8 = 1, kFmtRgba8 = 2, kFmtBgra8 = 3, kFmtRgb8Planar = 4, kFmtCount = 5;
 // full-range 8-bit Y, Cb, Cr samples (no colour conversion; a sample v is the fp64 value v - 128):
 // NV12 (Y plane + one plane of interleaved Cb,Cr at half size), I420 (Y, Cb, Cr planes,
@@ -110,18 +111,6 @@ JPGE_HD inline uint32_t bayer_rgb(uint32_t phase, uint32_t y, uint32_t x, uint32
     }
     return dy ? hi | (mid << 8) | (lo << 16) : lo | (mid << 8) | (hi << 16);
 }
-JPGE_HD inline bool fmt_valid(int fmt) {
-    return (fmt >= 0 && fmt < kFmtCount) || fmt == kFmtGray8 || fmt_bayer(fmt) || (fmt >= kFmtNv12 && fmt <= kFmtYuv444Planar) ||
-           (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt == kFmtP010 || fmt == kFmtI010 ||
-           (fmt >= kFmtY210 && fmt <= kFmtI210) || fmt == kFmtV210;
-}
-JPGE_HD inline bool fmt_gray(int fmt) { return fmt == kFmtGray8; }
-JPGE_HD inline bool fmt_yuv(int fmt) { return fmt >= kFmtNv12; }
-JPGE_HD inline bool fmt_yuv422p10(int fmt) { return (fmt >= kFmtY210 && fmt <= kFmtI210) || fmt == kFmtV210; }  // 10-bit, chroma at half width, every row
-JPGE_HD inline bool fmt_yuv10(int fmt) { return fmt == kFmtP010 || fmt == kFmtI010 || fmt_yuv422p10(fmt); }  // 10-bit samples (in 16-bit words; v210: three to a 32-bit word)
-JPGE_HD inline bool fmt_yuv420(int fmt) { return fmt == kFmtNv12 || fmt == kFmtI420 || fmt == kFmtP010 || fmt == kFmtI010; }  // chroma planes at half size
-JPGE_HD inline bool fmt_yuv422(int fmt) { return (fmt >= kFmtYuyv && fmt <= kFmtI422) || fmt_yuv422p10(fmt); }  // chroma at half width, every row
-JPGE_HD inline bool fmt_packed422(int fmt) { return fmt == kFmtYuyv || fmt == kFmtUyvy; }  // (8-bit: 4-byte groups)
 constexpr int kShapeRgb8 = 0;    // 48 bytes R,G,B,...: three b128 loads
 constexpr int kShapeBgr8 = 1;    // the same loads, bytes 2,1,0 of each pixel
 constexpr int kShapeX4 = 2;      // RGBA8 / BGRA8: 64 bytes, four b128 loads, a wave-uniform byte selector
@@ -140,48 +129,9 @@ constexpr int kShapeP210 = 14;   // the P010 shape's four loads, the Cb,Cr row t
 constexpr int kShapeI210 = 15;   // the I010 shape's four loads, the chroma rows those of the pixels
 constexpr int kShapeV210 = 16;   // the three or four 16-byte groups that hold the run: four b128 loads, a per-lane phase
 constexpr int kShapeBayer8 = 17; // 16 raw bytes of rows y - 1, y, y + 1 and the six bytes beside them: three b128 and six byte loads
-JPGE_HD inline int fmt_shape(int fmt) {
-    return fmt_bayer(fmt) ? kShapeBayer8 : fmt == kFmtV210 ? kShapeV210 : fmt == kFmtY210 ? kShapeY210 : fmt == kFmtP210 ? kShapeP210 : fmt == kFmtI210 ? kShapeI210 : fmt == kFmtP010 ? kShapeP010 : fmt == kFmtI010 ? kShapeI010 : fmt_packed422(fmt) ? kShapePacked422 : fmt == kFmtNv16 ? kShapeNv16 : fmt == kFmtI422 ? kShapeI422 : fmt == kFmtGray8 ? kShapeGray : fmt == kFmtRgb8 ? kShapeRgb8 : fmt == kFmtBgr8 ? kShapeBgr8 : fmt == kFmtRgb8Planar ? kShapePlanar
-         : fmt == kFmtNv12 ? kShapeNv12 : fmt == kFmtI420 ? kShapeI420 : fmt == kFmtYuv444Planar ? kShapeYuv444 : kShapeX4;
-}
-// bytes per pixel within a row (planar: of one plane), and planes
-// (v210: 0, a row is no whole number of bytes per pixel; fmt_row_bytes has its rows)
-JPGE_HD inline uint64_t v210_row_bytes(uint32_t width) { return 16 * (((uint64_t)width + 5) / 6); }
-JPGE_HD inline uint32_t fmt_bpp(int fmt) { return fmt == kFmtV210 ? 0u : fmt_packed422(fmt) || fmt_yuv10(fmt) ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) || fmt_gray(fmt) || fmt_bayer(fmt) ? 1u : fmt >= kFmtRgba8 ? 4u : 3u; }
-JPGE_HD inline uint32_t fmt_planes(int fmt) { return fmt_packed422(fmt) || fmt == kFmtY210 || fmt == kFmtV210 ? 1u : fmt == kFmtNv12 || fmt == kFmtNv16 || fmt == kFmtP010 || fmt == kFmtP210 ? 2u : fmt == kFmtRgb8Planar || fmt_yuv(fmt) ? 3u : 1u; }
-// The least row pitch of a frame's first plane (NV12: the width rounded up to even, so
-// that the Cb,Cr rows of the same pitch hold ceil(width / 2) pairs; NV16 likewise; the packed
-// 4:2:2 layouts: ceil(width / 2) whole 4-byte groups; Y210: whole 8-byte groups; v210: ceil(width / 6)
-// whole 16-byte groups).
-JPGE_HD inline uint64_t fmt_row_bytes(int fmt, uint32_t width) {
-    if (fmt_packed422(fmt)) return 4 * (((uint64_t)width + 1) / 2);
-    if (fmt == kFmtY210) return 8 * (((uint64_t)width + 1) / 2);
-    if (fmt == kFmtV210) return v210_row_bytes(width);
-    if (fmt == kFmtP010 || fmt == kFmtP210) return 2 * (((uint64_t)width + 1) & ~(uint64_t)1);  // (16-bit words; I010, I210: 2 * width, by fmt_bpp)
-    return fmt == kFmtNv12 || fmt == kFmtNv16 ? ((uint64_t)width + 1) & ~(uint64_t)1 : (uint64_t)fmt_bpp(fmt) * width;
-}
-// The 4:2:0 layouts' chroma: ceil(height / 2) rows of ceil(width / 2) samples, starting
-// plane_stride bytes after the Y plane; row pitch `stride` (NV12, 2 bytes per sample) or
-// (stride + 1) / 2 (I420, whose Cr plane follows the Cb plane's rows).  NV16 and I422: the
-// same pitches and order, `height` rows of ceil(width / 2) samples.
-// I010: 2 * ceil(stride / 4), whole 16-bit words; P010: stride.  P210 and I210: the same pitches
-// and order, `height` rows.
-JPGE_HD inline uint64_t fmt_chroma_pitch(int fmt, uint64_t stride) {
-    return fmt == kFmtI010 || fmt == kFmtI210 ? 2 * ((stride + 3) / 4) : fmt == kFmtI420 || fmt == kFmtI422 ? (stride + 1) / 2 : stride;
-}
 JPGE_HD inline uint32_t chroma_dim(uint32_t n) { return (n + 1) / 2; }
-// The transform kernel reaches a frame's pixels and its coefficients through 32-bit buffer
-// offsets: stride * height (planar layouts: of one plane; each plane has a descriptor of its
-// own, the chroma planes' extents are no larger) and nblocks * 128 must stay below this bound
-// (fdct.hip's out-of-range offset).  The frame entries refuse a frame that does not fit
-// with the argument error, before anything is queued (jpge.h, jpge_frame.stride).
+// K1's out-of-range buffer offset (fdct.hip kOob), the bound of layouts.hpp k1_offsets_fit
 constexpr uint64_t kK1OffsetBound = 0xFFFFFF00u;
-inline bool k1_offsets_fit(int fmt, const Geometry& g, uint64_t stride) {
-    const uint64_t row = fmt_row_bytes(fmt, g.width);
-    if (g.height == 0 || stride < row || stride >= kK1OffsetBound) return false;
-    const uint64_t extent = stride * (g.height - 1) + row;  // the descriptor's range
-    return extent < kK1OffsetBound && stride * g.height < kK1OffsetBound && (uint64_t)g.nblocks() * 128 < kK1OffsetBound;
-}
 
 constexpr int kHistReplicas = 8;  // spread of the global histogram atomics
 constexpr int kStatsTile = 128;           // blocks per statistics tile (4 lanes each)
@@ -265,7 +215,6 @@ inline void fdct_set_lut(FdctArgs& a, const uint8_t* d_lut) { a.xf[0] = __builti
 // Box downscale by 2 or 4 inside K1 (jpge.h jpge_set_downscale): the interleaved RGB layouts in
 // every subsampling mode, and NV12 (whose Cb,Cr plane is averaged in its own domain).
 JPGE_HD inline bool ds_valid(int ds) { return ds == 1 || ds == 2 || ds == 4; }
-JPGE_HD inline bool ds_fmt(int fmt) { return (fmt >= kFmtRgb8 && fmt <= kFmtBgra8) || fmt == kFmtNv12; }
 JPGE_HD inline uint32_t ds_dim(uint32_t n, int ds) { return (n + (uint32_t)ds - 1) / (uint32_t)ds; }
 
 // Orientation applied inside K1 (jpge.h jpge_set_orientation, the same values): the coded frame
@@ -278,7 +227,6 @@ JPGE_HD inline bool orient_valid(int o) { return o >= 0 && o <= 7; }
 JPGE_HD inline bool orient_transposed(int o) { return o >= 4; }
 JPGE_HD inline bool orient_mirrored(int o) { return ((0xC6u >> o) & 1u) != 0; }   // 1, 2, 6, 7
 JPGE_HD inline bool orient_rows_back(int o) { return ((0x6Cu >> o) & 1u) != 0; }  // 2, 3, 5, 6
-JPGE_HD inline bool orient_fmt(int fmt) { return fmt >= kFmtRgb8 && fmt <= kFmtBgra8; }
 JPGE_HD inline uint32_t orient_w(uint32_t w, uint32_t h, int o) { return orient_transposed(o) ? h : w; }
 JPGE_HD inline uint32_t orient_h(uint32_t w, uint32_t h, int o) { return orient_transposed(o) ? w : h; }
 // the source pixel (row sr, column sc) of O(y, x)
